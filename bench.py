@@ -7,12 +7,18 @@ binners (one merged pass, as ExecutorLocal merges them), 1e9 float64 rows per GP
 N > 1 GPUs the rows are sharded by rank and the dense grids are all-reduced over RCCL.
 Fresh aggregator grids are created in every step (as a query does), and every step reads
 both grids back to host numpy arrays (get_result, cpu.py:592-605) inside the timed region.
-The roofline's kernel durations come from HIP events in a second, instrumented run of the
-same steps (no timers inside the timed region).
 
-Prints ONE JSON line (rank 0) with the roofline of the binning pipeline (HIP events on the
-library stream) and the CPU baseline (the oracle's C restatement with the reference
-threading model, on a bounded sample, rank 0 at N=1 only).
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) does only what the headline figure
+needs: it generates the columns, warms up, times the N steps, writes the last timed step's
+grids when ``--dump-outputs DIR`` is given, and prints ONE JSON line (rank 0) with ``metric``,
+``value``, ``unit``, ``higher_is_better``, ``dtype`` and ``ms_per_step``.
+
+``--full`` adds everything else to that line: the roofline of the binning pipeline (kernel
+durations from HIP events in a second, instrumented run of the same steps; no timers inside
+the timed region), the full-size property checks, the other legs (count-only, float32,
+selections, groupby, h2o, C4, C1, host columns, the multi-GPU legs) and the CPU baseline
+(the oracle's C restatement with the reference threading model, on a bounded sample, rank 0
+at N=1 only).  The ``--no-*`` / ``--*-rows`` options select among those legs.
 """
 import argparse
 import json
@@ -38,6 +44,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--rows", type=float, default=1e9, help="rows per GPU")
     p.add_argument("--bins", type=int, default=1024)
+    p.add_argument("--full", action="store_true",
+                   help="also run the roofline's instrumented steps, the property checks, the other legs and the "
+                        "CPU baseline (the --no-* and --*-rows options below choose among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's grids to DIR/count.npy and DIR/sum.npy "
+                        "(float64, as the caller receives them; rank 0)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline work")
     p.add_argument("--no-groupby", action="store_true")
@@ -62,7 +74,10 @@ def parse():
                    help="(launcher test) every rank prints its rank environment and exits before any GPU call")
     p.add_argument("--dry-launch-fail-rank", type=int, default=-1,
                    help="(launcher test) with --dry-launch, this rank exits with status 3")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args, argv):
@@ -195,6 +210,64 @@ def main():
     total_rows = n * world * args.steps
     value = total_rows / elapsed
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+
+    roofline, check, extra, cpu = None, None, {}, None
+    if args.full:
+        roofline, check, extra, cpu = full_legs(args, rank, world, dist, x, y, w, n, bins, step, res, ms_per_step)
+
+    if rank == 0:
+        line = {
+            "metric": BASELINE_METRIC,
+            "value": value,
+            "unit": "rows/s",
+            "n_gpus": rccl_ranks if rccl_ranks is not None else world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic: x,y ~ N(0,1), w ~ U[0,1) float64 generated in HBM (counter-based splitmix64)",
+            "config": {
+                "workload": "C2 (BASELINE configs[1]): count(binby=[x,y], limits=[[-4,4],[-4,4]], shape=1024)"
+                            " + sum(w), one merged pass",
+                "rows_per_gpu": n,
+                "grid": [bins + 3, bins + 3],
+                "parallelism": f"row-shard x{world}" + (" + RCCL grid all-reduce" if world > 1 else ""),
+                "rccl_ranks": rccl_ranks,
+            },
+            "full": args.full,
+            "roofline": roofline,
+            "cpu_baseline": cpu,
+        }
+        if check is not None:
+            line["check"] = check
+        line.update(extra)
+        print(json.dumps(line), flush=True)
+    if dist is not None:
+        vdist.shutdown()
+
+
+def dump_outputs(path, res):
+    """``--dump-outputs``: the grids the last timed step returned to its caller (count, an
+    int64 grid whose cells are far below 2**53, and sum(w), both (bins + 3)^2), each as
+    float64 in ``<path>/<name>.npy``; 2 x 8.4 MB at the default 1024 bins."""
+    os.makedirs(path, exist_ok=True)
+    count, total = res
+    np.save(os.path.join(path, "count.npy"), np.asarray(count).astype(np.float64))
+    np.save(os.path.join(path, "sum.npy"), np.asarray(total).astype(np.float64))
+
+
+def full_legs(args, rank, world, dist, x, y, w, n, bins, step, res, ms_per_step):
+    """``--full``: everything the result line holds beyond the headline figure; returns
+    (roofline, check, extra legs, CPU baseline)."""
+    import vaex_amd
+    from vaex_amd import _lib
+    from vaex_amd import distributed as vdist
+
     # per-kernel HIP-event durations from a separate instrumented run of the same steps
     _lib.timing_reset()
     _lib.timing_enable(True)
@@ -292,37 +365,7 @@ def main():
             cpu["groupby"], check["prefix_oracle"]["c3"] = cpu_baseline_groupby()
         check["ok"] = bool(check["ok"] and all(v.get("ok") for v in check["prefix_oracle"].values()))
         extra["c1"] = bench_c1(args)
-
-    if rank == 0:
-        line = {
-            "metric": BASELINE_METRIC,
-            "value": value,
-            "unit": "rows/s",
-            "n_gpus": rccl_ranks if rccl_ranks is not None else world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic: x,y ~ N(0,1), w ~ U[0,1) float64 generated in HBM (counter-based splitmix64)",
-            "config": {
-                "workload": "C2 (BASELINE configs[1]): count(binby=[x,y], limits=[[-4,4],[-4,4]], shape=1024)"
-                            " + sum(w), one merged pass",
-                "rows_per_gpu": n,
-                "grid": [bins + 3, bins + 3],
-                "parallelism": f"row-shard x{world}" + (" + RCCL grid all-reduce" if world > 1 else ""),
-                "rccl_ranks": rccl_ranks,
-            },
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
-        line["check"] = check
-        line.update(extra)
-        print(json.dumps(line), flush=True)
-    if dist is not None:
-        vdist.shutdown()
+    return roofline, check, extra, cpu
 
 
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_c2.json")

@@ -5,7 +5,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=$1; VAR=$2
 : > $OUT
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-groupby --no-layouts --no-aggs --no-set --no-count-only --no-f32 --no-filtered --host-rows 0 --c4-rows 0 --h2o-rows 0"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-groupby --no-layouts --no-aggs --no-set --no-count-only --no-f32 --no-filtered --host-rows 0 --c4-rows 0 --h2o-rows 0"
 for r in $(seq ${ROUNDS:-2}); do
   for tag in cur var; do
     if [ $tag = var ]; then
