@@ -184,7 +184,6 @@ struct Workspace {
     DevBuf cells;                                 // small-grid path: u16 cell per row
     DevBuf first_part;                            // small-grid AggFirst: per-workgroup (key, row) partials
     HostPipe pipe;                                // host-column staging
-    DevBuf tile_entries, tile_values, tile_meta;  // tiled path
     ~Workspace();
 };
 

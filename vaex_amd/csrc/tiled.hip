@@ -36,18 +36,12 @@
 #include "binner_dev.hpp"
 #include "common.hpp"
 #include "engine.hpp"
+#include "tile_plan.hpp"  // the host planner, and the constants it shares with the kernels
 
 namespace vh {
 
-#ifndef VH_TA_THREADS
-#define VH_TA_THREADS 512
-#endif
 #ifndef VH_TA_WAVES
 #define VH_TA_WAVES 0  // amdgpu_waves_per_eu floor for pass A (0 = compiler's choice)
-#endif
-constexpr int TA_THREADS = VH_TA_THREADS;
-#ifndef VH_TA_RPT
-#define VH_TA_RPT 8
 #endif
 #ifndef VH_TA_NT
 #define VH_TA_NT 0
@@ -58,91 +52,7 @@ constexpr int TA_THREADS = VH_TA_THREADS;
 // (profiles/r06_drain_inproc.txt); a run-time choice cost the count-only kernel 48 spilled VGPRs
 #define VH_TA_DRAIN 1
 #endif
-#ifndef VH_TB_THREADS
-#define VH_TB_THREADS 1024
-#endif
-constexpr int TA_RPT = VH_TA_RPT;
-constexpr int TA_BATCH = TA_THREADS * TA_RPT;
-constexpr int TB_THREADS = VH_TB_THREADS;
-#ifndef VH_TILE_LDS_KB
-#define VH_TILE_LDS_KB 96
-#endif
-constexpr uint64_t TILE_LDS_BUDGET = VH_TILE_LDS_KB * 1024;
-constexpr uint32_t TILE_MAX_TILES = 4096;
-constexpr size_t LDS_MAX_BYTES = 160 * 1024;  // per workgroup on gfx950
-constexpr int TA_WG_PER_CU = 4;
-constexpr int SAMPLE_BLOCKS = 512;
 
-enum : int32_t { CNT_ALWAYS = -2, CNT_FLAG = -1 };
-
-struct TileParams {
-    uint32_t s_log2, ntiles, flags_mode, nvals;
-    uint64_t cells;
-    uint32_t W;                // pass-A workgroups
-    uint32_t pad;
-    uint64_t rows_per_wg;      // upper bound (region sizing): batches of a workgroup x TA_BATCH
-    uint64_t wg_stride;        // entries of one workgroup's regions
-    const uint32_t *cap;       // [T]
-    const uint64_t *toff;      // [T] region offset inside a workgroup's block
-    uint32_t *fills;           // [T][W] entries produced (may exceed cap)
-    // spill areas: rows past their (workgroup, tile) region go to their tile's spill area
-    // (one atomic reservation per tile and commit), read by pass B like one more region;
-    // past the spill area too (should not happen): global atomics
-    uint32_t *spill_fill;         // [T] entries reserved (may exceed spill_cap)
-    const uint32_t *spill_cap;    // [T]
-    const uint64_t *spill_start;  // [T] entry index of the area, relative to spill_base
-    uint64_t spill_base;          // first entry of the spill areas (after the W regions)
-    void *entries;             // u16 / u32, W * wg_stride
-    double *values[2];         // per value slot, W * wg_stride
-    int32_t val_slot[MAX_FUSED_AGGS];  // sum agg k -> value slot
-    int32_t cnt_slot[MAX_FUSED_AGGS];  // count agg k -> CNT_ALWAYS / CNT_FLAG / value slot
-    const double *vdata[2];    // value slot -> source column (fast kernel)
-    uint32_t debug;            // experiment switches (VH_TILE_DEBUG), ablation build only (DBG)
-    // 4-byte value slots (every summed column <= 4 bytes: int8/16/32, uint8/16/32, bool,
-    // float32 -- exact): slot s is float32 bits when bit s of vfloat is set, else the low 32
-    // bits of the int64 slot, sign-extended back when bit s of vsigned is set
-    uint32_t vnarrow, vfloat, vsigned;
-    // two narrow slots in one array: values[0] holds, per 8 entries, their 8 slot-0 values then
-    // their 8 slot-1 values (the narrow ordinal pass A with two carried columns: one write
-    // stream, not two; pass B still reads each slot as 32 contiguous bytes)
-    uint32_t vpacked;
-    int32_t vdt[2];            // value slot -> column dtype (fast ordinal kernel)
-    // min / max aggregator k: pass B flushes its LDS cells with native global atomics into
-    // mmtmp[k] (cells x 4 or 8 bytes of the LDS cell form, identity-filled), merged into the
-    // typed grid afterwards by k_mm_merge (a CAS per cell on 1- and 2-byte grids serialised
-    // on the shared words)
-    void *mmtmp[MAX_FUSED_AGGS];
-    // pass B with min / max / moment: mgeneric, a moment other than 2 (per-entry form); mmk, bit
-    // k set when aggregator k is a min / max (its cells are read ahead of each chunk)
-    uint32_t mgeneric, mmk;
-    // wide stream-out of the fast kernels (batch_commit_fast): every (workgroup, tile) run of
-    // a commit is padded to a multiple of 8 entries with DUMMY_CELL entries, so runs start
-    // 8-aligned in the region and a lane stores 8 cells / 2 float64 values / 4 narrow slots
-    // per 16-byte store; pass B skips the dummies.  lds_cap: staged entries per value slot
-    uint32_t wide, lds_cap;
-    // min / max pass B on one float64 value slot with at most one count, sum, min and max
-    // aggregator of it (no moments, no integer sums): a branch-light entry loop (mm_simple);
-    // LDS byte offsets of the count / sum / min / max cells (-1: absent), the count keyed on
-    // the slot's non-NaN values (mm_cnt_nn) or on every entry
-    uint32_t mm_simple, mm_cnt_nn;
-    int32_t mm_off[4];
-    // stream layout of the fast kernels (stream = 1): each pass-A workgroup appends every
-    // commit's padded, tile-sorted entries to ONE contiguous stream (w * wg_stride on), instead
-    // of T private per-tile regions, and records where each tile's run of the commit starts:
-    // tab[(w * (T + 1) + t) * ncw + c] = stream offset of tile t's run of commit c (row T: the
-    // commit's end; commits past a workgroup's last: its final offset, i.e. empty runs).  Pass B
-    // gathers a tile's (workgroup, commit) segments through the table.  256-512 write streams
-    // instead of T x W regions: the region pattern's cost and its dependence on where the
-    // scratch lands in HBM (r05: 6.2-7.4 ms for one C2 pass A) go away (scripts/bw_probe6.hip)
-    uint32_t stream, ncw;
-    uint32_t *tab;
-    // one keep mask shared by every aggregator (a selection or filter; 1 = keep) applied by the
-    // fast pass A per row: masked rows are dropped before the exchange (MK instantiations)
-    const uint8_t *rowmask;
-};
-
-// local cell of a padding entry (tiles hold at most 2^15 cells when runs are padded)
-constexpr uint32_t DUMMY_CELL = 0xffffu;
 typedef unsigned int vh_u32x4 __attribute__((ext_vector_type(4)));
 typedef double vh_f64x2 __attribute__((ext_vector_type(2)));
 // a 16-byte region store, non-temporal when nt (wave-uniform)
@@ -209,7 +119,6 @@ __device__ __forceinline__ double slot_wide(uint32_t u, bool is_float, bool is_s
 // unsigned: uint64), cells start at the kind's identity, and touched cells are flushed into
 // the typed grid with the CAS min / max of the generic path (std::min/max semantics; NaN
 // never enters, as the reference's comparisons skip it).
-__host__ __device__ inline bool is_minmax(int kind) { return kind == VH_AGG_MIN || kind == VH_AGG_MAX; }
 __device__ inline bool dt_float(int dt) { return dt == VH_F64 || dt == VH_F32; }
 __device__ inline bool dt_signed(int dt) { return dt == VH_I64 || dt == VH_I32 || dt == VH_I16 || dt == VH_I8; }
 __device__ inline uint64_t ord_bits(double d) {
@@ -246,12 +155,6 @@ __device__ inline void mm_lds(uint64_t *cell, int dt, bool mx, double v) {
         if (mx) atomicMax((unsigned long long *)cell, x);
         else atomicMin((unsigned long long *)cell, x);
     }
-}
-// 4-byte LDS cells for min / max of <= 4-byte columns (ds_min/max_i32 / _u32: half the LDS
-// of the 64-bit form, and 32-bit LDS atomics): signed as int32, unsigned as uint32, float32
-// as order-preserving bits
-__host__ __device__ inline bool mm_cell32(int dt) {
-    return dt == VH_F32 || dt == VH_I32 || dt == VH_U32 || dt == VH_I16 || dt == VH_U16 || dt == VH_I8 || dt == VH_U8;
 }
 __device__ inline uint32_t mm_identity32(int dt, bool mx) {
     if (dt_signed(dt)) return mx ? (uint32_t)INT32_MIN : (uint32_t)INT32_MAX;
@@ -367,10 +270,6 @@ __global__ __launch_bounds__(256) void k_mm_merge(void *grid, const void *tmp, u
         }
     }
 }
-
-struct WorkUnit {
-    uint32_t tile, w_begin, w_end, pad;
-};
 
 template <int ND> __device__ inline uint64_t cell_of(const BinPlan &p, uint64_t i) {
     if constexpr (ND == 0) {
@@ -545,11 +444,6 @@ struct ScatterLds {
     uint32_t *hist, *boff, *base, *lim, *dbase, *soff, *wave_sums;
 };
 
-// LDS bytes of pass A (must match scatter_lds)
-__host__ __device__ inline size_t scatter_lds_bytes(int nv, uint32_t T) {
-    return (size_t)8 * nv * TA_BATCH + (size_t)8 * TA_BATCH + 24 * (size_t)T + 64;
-}
-
 template <int NV> __device__ inline ScatterLds scatter_lds(unsigned char *raw, uint32_t T) {
     ScatterLds l;
     l.sv = reinterpret_cast<double *>(raw);
@@ -562,30 +456,6 @@ template <int NV> __device__ inline ScatterLds scatter_lds(unsigned char *raw, u
     l.soff = l.dbase + T;
     l.wave_sums = l.soff + T;
     return l;
-}
-
-// rows per thread of one commit of the fast f64 pass A: with sums, SB batches are ranked
-// into one commit, so each (workgroup, tile) run is SB times longer (fewer, longer region
-// stores; the kernel already runs one workgroup per CU on registers)
-#ifndef VH_TA_SB
-#define VH_TA_SB 3
-#endif
-#ifndef VH_TA_SB0
-#define VH_TA_SB0 2  // count-only commits (same-process A/B: 1 -> 2 is 3.99 -> 3.87 ms, 3 is 4.08)
-#endif
-__host__ __device__ constexpr int fast_sb(int nv) { return nv == 0 ? VH_TA_SB0 : nv == 1 ? VH_TA_SB : (VH_TA_SB < 2 ? VH_TA_SB : 2); }
-// the 3-d f64 pass A carries a third binner column: fewer batches per commit keep its
-// registers out of scratch memory (three batches of one value slot spilled 17 VGPRs)
-__host__ __device__ constexpr int fast_sb_nd(int nv, int nd) {
-    return nd < 3 ? fast_sb(nv) : nv >= 2 ? 1 : (fast_sb(nv) < 2 ? fast_sb(nv) : 2);
-}
-// narrow (4-byte) value slots staged as 4 bytes: two carried columns still fit three batches
-__host__ __device__ constexpr int fast_sb_narrow(int nv) { return nv == 0 ? VH_TA_SB0 : VH_TA_SB; }
-
-// LDS of the fast kernels: staged values (vbytes each: 8, or 4 for narrow slots) | staged
-// 4-byte keys | tile arrays
-__host__ __device__ inline size_t fast_lds_bytes(int nv, uint32_t T, uint32_t cap, int vbytes = 8) {
-    return (size_t)vbytes * nv * cap + (size_t)4 * cap + 24 * (size_t)T + 64;
 }
 
 template <int NV> __device__ inline ScatterLds fast_lds(unsigned char *raw, uint32_t T, uint32_t cap, int vbytes = 8) {
@@ -627,9 +497,6 @@ __device__ inline void stream_tab_tail(const ScatterLds &l, const TileParams &tp
     for (uint32_t i = threadIdx.x; i < (T + 1) * per; i += TA_THREADS)
         tp.tab[(row0 + i / per) * ncw + c0 + i % per] = cend;
 }
-
-constexpr uint32_t DEST_OVERFLOW = 0x80000000u;  // | tile: region and spill full, global atomics
-constexpr uint32_t DEST_SPILL = 0x40000000u;     // | entry of the spill areas
 
 // phases 2-5 of a batch, after every row has its tile, entry, rank (-1 = drop) and
 // carried values: exclusive scan of the tile histogram; every row computes its final
@@ -2154,239 +2021,301 @@ __global__ __launch_bounds__(TBT) void k_tile_reduce(FusedAggs fa, TileParams tp
     }
 }
 
-// integer binner kernels (fast modes 8-11): int32 / int64 binners, float64 (or no) / float32 values
-template <int ND, int NV, typename F> static void int_kernel(int fast, F &&f) {
-    if constexpr (NV == 0) {
-        if (fast == 8) f(k_tile_scatter_f64<ND, 0, fast_sb_nd(0, ND), int32_t, false, double>);
-        else f(k_tile_scatter_f64<ND, 0, fast_sb_nd(0, ND), int64_t, false, double>);
-    } else {
-        switch (fast) {
-        case 8: f(k_tile_scatter_f64<ND, NV, fast_sb_nd(NV, ND), int32_t, false, double>); break;
-        case 9: f(k_tile_scatter_f64<ND, NV, fast_sb_narrow(NV), int32_t, false, float>); break;
-        case 10: f(k_tile_scatter_f64<ND, NV, fast_sb_nd(NV, ND), int64_t, false, double>); break;
-        default: f(k_tile_scatter_f64<ND, NV, fast_sb_narrow(NV), int64_t, false, float>);
-        }
+// ---- the kernels behind the planner's descriptors: the only place that names pass-A and pass-B
+// instantiations (one address for the occupancy query and the launch); nullptr: no such kernel
+#define VH_KP(...) reinterpret_cast<const void *>(__VA_ARGS__)
+template <int ND, int NV> static const void *fast_kernel(const PassAKernel &k) {
+    constexpr int SBW = fast_sb_nd(NV, ND), SBN = fast_sb_narrow(NV);  // commits of 8- / 4-byte values
+#define VH_FAST(CT_, VT_, MK_, SB_, ...) \
+    if (k.ct == (CT_) && k.vt == (VT_) && k.mk == (MK_) && k.sb == (SB_)) return VH_KP(k_tile_scatter_f64<ND, NV, SB_, __VA_ARGS__>);
+    VH_FAST(VH_F64, VH_F64, true, SBW, double, true)
+    VH_FAST(VH_F64, VH_F64, false, 1, double)
+    VH_FAST(VH_F64, VH_F64, false, SBW, double)
+    VH_FAST(VH_F32, VH_F32, true, SBN, float, true)
+    VH_FAST(VH_F32, VH_F32, false, SBN, float)
+    if constexpr (NV > 0) {  // mixed float plans carry values
+        VH_FAST(VH_F32, VH_F64, false, SBW, float, false, double)
+        VH_FAST(VH_F64, VH_F32, false, SBN, double, false, float)
     }
-}
-template <int ND, int NV>
-static void launch_scatter_int(int fast, unsigned grid, size_t lds, const BinPlan &plan, const FusedAggs &fa,
-                               const TileParams &tp, uint64_t n) {
-    int_kernel<ND, NV>(fast, [&](auto kern) {
-        BinPlan p = plan;
-        FusedAggs f = fa;
-        TileParams t = tp;
-        uint64_t nn = n;
-        void *args[] = {(void *)&p, (void *)&f, (void *)&t, (void *)&nn};
-        VH_HIP(hipLaunchKernel(reinterpret_cast<const void *>(kern), dim3(grid), dim3(TA_THREADS), args, lds, stream()));
-    });
-}
-template <int ND, int NV> static int scatter_int_blocks(int fast, size_t lds) {
-    int nb = 0;
-    int_kernel<ND, NV>(fast, [&](auto kern) {
-        VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kern), TA_THREADS, lds));
-    });
-    return nb;
-}
-
-// fast: 0 = generic kernel, 1 = fast kernel one batch per commit, 2 = fast kernel with
-// fast_sb(NV) batches per commit (when its LDS fits)
-template <int ND, int NV>
-static void launch_scatter(int fast, unsigned grid, size_t lds, const BinPlan &plan, const FusedAggs &fa,
-                           const TileParams &tp, uint64_t n) {
-    if constexpr (ND > 0) {
-        if (fast == 5 && tp.rowmask) {
-            hipLaunchKernelGGL((k_tile_scatter_f64<ND, NV, fast_sb_narrow(NV), float, true>), dim3(grid), dim3(TA_THREADS), lds, stream(), plan, fa, tp, n);
-            return;
-        }
-        if (fast == 2 && tp.rowmask) {
-            hipLaunchKernelGGL((k_tile_scatter_f64<ND, NV, fast_sb_nd(NV, ND), double, true>), dim3(grid), dim3(TA_THREADS), lds, stream(), plan, fa, tp, n);
-            return;
-        }
-        if (fast == 5) {
-            hipLaunchKernelGGL((k_tile_scatter_f64<ND, NV, fast_sb_narrow(NV), float>), dim3(grid), dim3(TA_THREADS), lds, stream(), plan, fa, tp, n);
-            return;
-        }
-        if constexpr (ND <= 2) {
-            if (fast >= 8 && fast <= 11) {
-                launch_scatter_int<ND, NV>(fast, grid, lds, plan, fa, tp, n);
-                return;
-            }
-        }
+    if constexpr (ND <= 2) {  // integer binners: 1- and 2-d
+        VH_FAST(VH_I32, VH_F64, false, SBW, int32_t, false, double)
+        VH_FAST(VH_I64, VH_F64, false, SBW, int64_t, false, double)
         if constexpr (NV > 0) {
-            if (fast == 6) {
-                hipLaunchKernelGGL((k_tile_scatter_f64<ND, NV, fast_sb_nd(NV, ND), float, false, double>), dim3(grid), dim3(TA_THREADS), lds, stream(), plan, fa, tp, n);
-                return;
-            }
-            if (fast == 7) {
-                hipLaunchKernelGGL((k_tile_scatter_f64<ND, NV, fast_sb_narrow(NV), double, false, float>), dim3(grid), dim3(TA_THREADS), lds, stream(), plan, fa, tp, n);
-                return;
-            }
-        }
-        if (fast == 2) {
-            hipLaunchKernelGGL((k_tile_scatter_f64<ND, NV, fast_sb_nd(NV, ND)>), dim3(grid), dim3(TA_THREADS), lds, stream(), plan, fa, tp, n);
-            return;
-        }
-        if (fast == 1) {
-            hipLaunchKernelGGL((k_tile_scatter_f64<ND, NV, 1>), dim3(grid), dim3(TA_THREADS), lds, stream(), plan, fa, tp, n);
-            return;
+            VH_FAST(VH_I32, VH_F32, false, SBN, int32_t, false, float)
+            VH_FAST(VH_I64, VH_F32, false, SBN, int64_t, false, float)
         }
     }
-    hipLaunchKernelGGL((k_tile_scatter<ND, NV>), dim3(grid), dim3(TA_THREADS), lds, stream(), plan, fa, tp, n);
+#undef VH_FAST
+    return nullptr;
 }
-
-template <int NV>
-static void launch_scatter_nd(int nd, int fast, unsigned grid, size_t lds, const BinPlan &plan, const FusedAggs &fa,
-                              const TileParams &tp, uint64_t n) {
-    switch (nd) {
-    case 1: launch_scatter<1, NV>(fast, grid, lds, plan, fa, tp, n); break;
-    case 2: launch_scatter<2, NV>(fast, grid, lds, plan, fa, tp, n); break;
-    case 3: launch_scatter<3, NV>(fast, grid, lds, plan, fa, tp, n); break;
-    case -1: launch_scatter<-1, NV>(0, grid, lds, plan, fa, tp, n); break;
-    default: launch_scatter<0, NV>(0, grid, lds, plan, fa, tp, n);
+// ordinal kernels by their compiled-in value dtypes, from the planner's own list (VH_ORD_COMBOS)
+template <int NV, int SB, bool SET, bool VN> static const void *ord_kernel(const PassAKernel &k) {
+    if (k.sb != SB) return nullptr;
+#define VH_ORD(a, b, narrow)                                                                   \
+    if constexpr ((!SET || (a) == VH_F64 || (a) < 0) && (!VN || narrow)) {                     \
+        constexpr int DT1 = (a) < 0 || NV >= 2 ? (b) : VH_F64;                                 \
+        if (k.dt0 == (a) && k.dt1 == DT1) return VH_KP(k_tile_scatter_ord<NV, SB, SET, (a), DT1, VN>); \
     }
+    VH_ORD_COMBOS(VH_ORD)
+#undef VH_ORD
+    return nullptr;
 }
-
-static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
-template <int ND, int NV> static int scatter_blocks_per_cu(int fast, size_t lds, bool mk) {
-    int nb = 0;
-    if constexpr (ND > 0) {
-        if (fast == 5 && mk) {
-            VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tile_scatter_f64<ND, NV, fast_sb_narrow(NV), float, true>, TA_THREADS, lds));
-            return nb;
-        }
-        if (fast == 2 && mk) {
-            VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tile_scatter_f64<ND, NV, fast_sb_nd(NV, ND), double, true>, TA_THREADS, lds));
-            return nb;
-        }
-        if (fast == 5) {
-            VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tile_scatter_f64<ND, NV, fast_sb_narrow(NV), float>, TA_THREADS, lds));
-            return nb;
-        }
-        if constexpr (ND <= 2) {
-            if (fast >= 8 && fast <= 11) return scatter_int_blocks<ND, NV>(fast, lds);
-        }
-        if constexpr (NV > 0) {
-            if (fast == 6) {
-                VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tile_scatter_f64<ND, NV, fast_sb_nd(NV, ND), float, false, double>, TA_THREADS, lds));
-                return nb;
-            }
-            if (fast == 7) {
-                VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tile_scatter_f64<ND, NV, fast_sb_narrow(NV), double, false, float>, TA_THREADS, lds));
-                return nb;
-            }
-        }
-        if (fast == 2) {
-            VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tile_scatter_f64<ND, NV, fast_sb_nd(NV, ND)>, TA_THREADS, lds));
-            return nb;
-        }
-        if (fast == 1) {
-            VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tile_scatter_f64<ND, NV, 1>, TA_THREADS, lds));
-            return nb;
-        }
-    }
-    VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_tile_scatter<ND, NV>, TA_THREADS, lds));
-    return nb;
-}
-
-template <int NV> static int scatter_blocks_per_cu_nd(int nd, int fast, size_t lds, bool mk) {
-    switch (nd) {
-    case 1: return scatter_blocks_per_cu<1, NV>(fast, lds, mk);
-    case 2: return scatter_blocks_per_cu<2, NV>(fast, lds, mk);
-    case 3: return scatter_blocks_per_cu<3, NV>(fast, lds, mk);
-    case -1: return scatter_blocks_per_cu<-1, NV>(0, lds, false);
-    default: return scatter_blocks_per_cu<0, NV>(0, lds, false);
-    }
-}
-
-// value-dtype combinations with their own ordinal kernel (0: float64; h2o's int8 / float32
-// sums; others take the run-time-switch kernel, -1)
-// narrow (VN) kernels: h2o's int8 / float32 combinations and the run-time switch
-template <int NV, int SB, typename F> static void ord_by_dts_narrow(int dt0, int dt1, F &&f) {
-#define VH_ORD_DT(a, b) if (dt0 == (a) && (NV < 2 || dt1 == (b))) return f(k_tile_scatter_ord<NV, SB, false, (a), NV < 2 ? VH_F64 : (b), true>);
-    VH_ORD_DT(VH_I8, VH_I8)
-    VH_ORD_DT(VH_I8, VH_F32)
-    VH_ORD_DT(VH_F32, VH_I8)
-    VH_ORD_DT(VH_F32, VH_F32)
-    VH_ORD_DT(VH_I32, VH_I32)
-#undef VH_ORD_DT
-    f(k_tile_scatter_ord<NV, SB, false, -1, -1, true>);
-}
-template <int NV, int SB, bool SET, typename F> static void ord_by_dts(int dt0, int dt1, F &&f) {
-#define VH_ORD_DT(a, b) if (dt0 == (a) && (NV < 2 || dt1 == (b))) return f(k_tile_scatter_ord<NV, SB, SET, (a), NV < 2 ? VH_F64 : (b)>);
-    VH_ORD_DT(VH_F64, VH_F64)
+template <bool SET> static const void *ord_kernel_set(const PassAKernel &k) {
     if constexpr (!SET) {
-        VH_ORD_DT(VH_I8, VH_I8)
-        VH_ORD_DT(VH_I8, VH_F32)
-        VH_ORD_DT(VH_F32, VH_I8)
-        VH_ORD_DT(VH_F32, VH_F32)
-        VH_ORD_DT(VH_I32, VH_I32)
-        VH_ORD_DT(VH_I32, VH_F64)
-        VH_ORD_DT(VH_F32, VH_F64)
-    }
-#undef VH_ORD_DT
-    f(k_tile_scatter_ord<NV, SB, SET, -1, -1>);
-}
-template <bool SET> static const void *ord_kernel_t(int nv, int fast_mode, int dt0, int dt1, bool mk) {
-    const void *k = nullptr;
-    auto take = [&](auto kern) { k = reinterpret_cast<const void *>(kern); };
-    if (mk) {  // shared keep mask: int32 key, float64 values (or none), batched commits
-        if constexpr (!SET) {
-            if (nv == 0) return reinterpret_cast<const void *>(k_tile_scatter_ord<0, 1, false, VH_F64, VH_F64, false, true>);
-            if (fast_mode != 2 || dt0 != VH_F64 || (nv > 1 && dt1 != VH_F64)) return nullptr;
-            return nv == 1 ? reinterpret_cast<const void *>(k_tile_scatter_ord<1, fast_sb(1), false, VH_F64, VH_F64, false, true>)
-                           : reinterpret_cast<const void *>(k_tile_scatter_ord<2, fast_sb(2), false, VH_F64, VH_F64, false, true>);
+        if (k.mk) {  // shared keep mask: float64 values (or none), batched commits
+            if (k.vn || k.dt0 != VH_F64 || k.dt1 != VH_F64) return nullptr;
+            if (k.nv == 0 && k.sb == 1) return VH_KP(k_tile_scatter_ord<0, 1, false, VH_F64, VH_F64, false, true>);
+            if (k.nv == 1 && k.sb == fast_sb(1)) return VH_KP(k_tile_scatter_ord<1, fast_sb(1), false, VH_F64, VH_F64, false, true>);
+            if (k.nv == 2 && k.sb == fast_sb(2)) return VH_KP(k_tile_scatter_ord<2, fast_sb(2), false, VH_F64, VH_F64, false, true>);
+            return nullptr;
         }
-        return nullptr;
+        if (k.vn)  // narrow slots, fast_sb_narrow(nv) batches per commit
+            return k.nv == 1 ? ord_kernel<1, fast_sb_narrow(1), false, true>(k) : k.nv == 2 ? ord_kernel<2, fast_sb_narrow(2), false, true>(k) : nullptr;
     }
-    if constexpr (!SET) {
-        if (fast_mode == 3) {  // narrow slots, fast_sb_narrow(nv) batches per commit
-            if (nv == 1) ord_by_dts_narrow<1, fast_sb_narrow(1)>(dt0, dt1, take);
-            else ord_by_dts_narrow<2, fast_sb_narrow(2)>(dt0, dt1, take);
-            return k;
-        }
+    if (k.mk || k.vn) return nullptr;
+    switch (k.nv) {
+    case 0: return ord_kernel<0, 1, SET, false>(k);
+    case 1: return k.sb == 1 ? ord_kernel<1, 1, SET, false>(k) : ord_kernel<1, fast_sb(1), SET, false>(k);
+    case 2: return k.sb == 1 ? ord_kernel<2, 1, SET, false>(k) : ord_kernel<2, fast_sb(2), SET, false>(k);
+    default: return nullptr;
     }
-    if (nv == 0) ord_by_dts<0, 1, SET>(VH_F64, VH_F64, take);
-    else if (nv == 1) {
-        if (fast_mode == 2) ord_by_dts<1, fast_sb(1), SET>(dt0, dt1, take);
-        else ord_by_dts<1, 1, SET>(dt0, dt1, take);
-    } else {
-        if (fast_mode == 2) ord_by_dts<2, fast_sb(2), SET>(dt0, dt1, take);
-        else ord_by_dts<2, 1, SET>(dt0, dt1, take);
-    }
-    return k;
 }
-static const void *ord_kernel(int nv, int fast_mode, bool set, int dt0, int dt1, bool mk = false) {
-    return set ? ord_kernel_t<true>(nv, fast_mode, dt0, dt1, mk) : ord_kernel_t<false>(nv, fast_mode, dt0, dt1, mk);
+template <int NV> static const void *pass_a_kernel_nv(const PassAKernel &k) {
+    if (k.family == PassAKernel::FAST)
+        return k.nd == 1 ? fast_kernel<1, NV>(k) : k.nd == 2 ? fast_kernel<2, NV>(k) : k.nd == 3 ? fast_kernel<3, NV>(k) : nullptr;
+    static const void *const generic[] = {VH_KP(k_tile_scatter<-1, NV>), VH_KP(k_tile_scatter<0, NV>), VH_KP(k_tile_scatter<1, NV>),
+                                          VH_KP(k_tile_scatter<2, NV>), VH_KP(k_tile_scatter<3, NV>)};
+    return k.sb == 1 && !k.mk && k.nd >= -1 && k.nd <= 3 ? generic[k.nd + 1] : nullptr;
+}
+const void *pass_a_kernel(const PassAKernel &k) {
+    if (k.family == PassAKernel::ORDINAL) return k.set ? ord_kernel_set<true>(k) : ord_kernel_set<false>(k);
+    return k.nv == 0 ? pass_a_kernel_nv<0>(k) : k.nv == 1 ? pass_a_kernel_nv<1>(k) : k.nv == 2 ? pass_a_kernel_nv<2>(k) : nullptr;
+}
+template <int NV, bool NARROW, bool PK> static const void *reduce_kernel(const PassBKernel &k) {
+    if (k.mg) return VH_KP(k_tile_reduce<NV, NARROW, true, PK, true>);
+    return k.mm ? VH_KP(k_tile_reduce<NV, NARROW, true, PK>) : VH_KP(k_tile_reduce<NV, NARROW, false, PK>);
+}
+const void *pass_b_kernel(const PassBKernel &k) {
+    if (k.nv == 0) return VH_KP(k_tile_reduce<0, false, false>);
+    if (k.pk) return reduce_kernel<2, true, true>(k);
+    if (k.nv == 1) return k.narrow ? reduce_kernel<1, true, false>(k) : reduce_kernel<1, false, false>(k);
+    return k.narrow ? reduce_kernel<2, true, false>(k) : reduce_kernel<2, false, false>(k);
+}
+static const void *sample_kernel(int nd_f64) {
+    static const void *const ks[] = {VH_KP(k_tile_sample<0>), VH_KP(k_tile_sample<1>), VH_KP(k_tile_sample<2>), VH_KP(k_tile_sample<3>)};
+    return ks[nd_f64 >= 1 && nd_f64 <= 3 ? nd_f64 : 0];
+}
+#undef VH_KP
+
+// blocks of `kernel` per CU with `lds` bytes of dynamic LDS, asked of the runtime once
+static int blocks_per_cu(const void *kernel, size_t lds) {
+    static std::mutex mu;
+    static std::map<std::tuple<int, const void *, size_t>, int> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    const auto key = std::make_tuple(current_device(), kernel, lds);
+    auto it = cache.find(key);
+    if (it == cache.end()) {
+        int v = 0;
+        VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, TA_THREADS, lds));
+        it = cache.emplace(key, v).first;
+    }
+    return it->second;
 }
 
-static bool try_tiled_impl(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64);
+// Partition scratch shared by every grid of a device: a 1e9-row count+sum needs ~10 GB of
+// regions, which a per-grid buffer would hipMalloc/hipFree for every query (a grid lives
+// for one query).  Held under the device's lock while a bin is enqueued; reuse is ordered
+// by the library stream.
+struct TileScratch {
+    std::mutex mu;
+    DevBuf entries, values, meta, mmtmp, tab;
+};
 
-// the fast ordinal pass A applies: one native int32 BinnerOrdinal without mask, every
-// sum a 16-byte aligned float64 column, no aggregator masks, no counts of other columns
-static bool ord_fast_ok(const BinPlan &plan, const FusedAggs &fa) {
-    if (plan.nb != 1) return false;
-    const BinnerDev &b = plan.b[0];
-    const bool set_ok = b.kind == 2 && (b.dtype == VH_I32 || b.dtype == VH_U32) && !b.set.wide;
-    if (!(b.kind == 1 && b.dtype == VH_I32) && !set_ok) return false;
-    if (b.flip || b.mask || (reinterpret_cast<uintptr_t>(b.data) & 7)) return false;
+// the VH_TILE_* switches, read on every call (tests and scripts/ change them between calls)
+static TileSwitches read_switches() {
+    auto off = [](const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; };  // NAME=0: off
+    TileSwitches sw;
+    sw.rowmask = !off("VH_TILE_ROWMASK");
+    sw.f32 = !off("VH_TILE_F32");
+    sw.narrow = !off("VH_TILE_NARROW");
+    sw.stream = !off("VH_TILE_STREAM");
+    sw.pack = !off("VH_TILE_PACK");
+    if (const char *e = getenv("VH_TILE_WIDE")) sw.wide = (uint32_t)atoi(e);
+    if (const char *e = getenv("VH_TILE_WGPAD")) sw.wgpad = (uint64_t)strtoull(e, nullptr, 10);
+#ifdef VH_ABLATION
+    if (const char *e = getenv("VH_TILE_DEBUG")) sw.debug = (uint32_t)atoi(e);
+#endif
+    return sw;
+}
+static TileScratch &tile_scratch() {
+    static std::mutex g;
+    static std::map<int, std::unique_ptr<TileScratch>> m;
+    std::lock_guard<std::mutex> lk(g);
+    auto &p = m[current_device()];
+    if (!p) p = std::make_unique<TileScratch>();
+    return *p;
+}
+
+static void launch(const void *kernel, unsigned grid, unsigned block, size_t lds, void **args) {
+    VH_HIP(hipLaunchKernel(kernel, dim3(grid), dim3(block), args, lds, stream()));
+    VH_HIP(hipGetLastError());
+}
+
+static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64,
+                           const uint8_t *rowmask, const TileSwitches &sw) {
+    TileScratch &ws = tile_scratch();
+    std::lock_guard<std::mutex> ws_lock(ws.mu);
+    TilePlan tpl;
+    if (!plan_tiles(plan, fa_in, n, cells, nd_f64, rowmask != nullptr, sw, tpl)) return false;
+    const void *kernel_a = pass_a_kernel(tpl.a), *kernel_b = pass_b_kernel(tpl.b);
+    if (!kernel_a || !kernel_b) fail(VH_ERR_RUNTIME, "tiled binning: the plan names a kernel that is not built");
+    const TileLaunch L = plan_launch(tpl, n, cu_count(), blocks_per_cu(kernel_a, tpl.lds_a), sw);
+    const uint32_t T = tpl.tp.ntiles, W = L.W;
+    const int nv = (int)tpl.tp.nvals;
+    hipStream_t st = stream();
+    FusedAggs fa = fa_in;
     for (int k = 0; k < fa.na; k++) {
-        const FusedAgg &a = fa.a[k];
-        if (a.mask) return false;
-        if (a.kind != VH_AGG_COUNT) {
-            // any native value dtype; pair loads need 2 x itemsize alignment
-            if (!a.data) return false;
-            const int isz = a.dtype == VH_F64 ? 16 : 2 * dtype_itemsize(a.dtype);
-            if (reinterpret_cast<uintptr_t>(a.data) % isz) return false;
-        } else if (a.data) {
-            bool keyed = false;  // count(v) of a summed column rides on that sum's value
-            for (int j = 0; j < fa.na; j++)
-                if (fa.a[j].kind != VH_AGG_COUNT && fa.a[j].data == a.data) keyed = true;
-            if (!keyed) return false;
+        fa.a[k].lds_off = tpl.lds_off[k];
+        if (fa.a[k].kind != VH_AGG_COUNT) tpl.tp.vdata[tpl.tp.val_slot[k]] = fa.a[k].data;
+    }
+    fa.lds_words = (uint32_t)(tpl.lds_b / 4);
+    TileParams &tp = tpl.tp;  // the planner's part; the launch's and the scratch pointers follow
+    tp.rowmask = rowmask, tp.debug = sw.debug;
+    tp.W = W, tp.rows_per_wg = L.rows_per_wg;
+    ws.meta.ensure(L.meta.bytes);
+    unsigned char *mb = ws.meta.as<unsigned char>();
+    auto u32 = [&](uint64_t off) { return reinterpret_cast<uint32_t *>(mb + off); };
+    auto u64 = [&](uint64_t off) { return reinterpret_cast<uint64_t *>(mb + off); };
+    uint64_t *d_hist = u64(L.meta.hist), *d_hist2 = d_hist + T;  // one array: [2][T]
+    uint32_t *d_brange = u32(L.meta.brange);
+    const WorkUnit *d_units = reinterpret_cast<const WorkUnit *>(mb + L.meta.units);
+    tp.cap = u32(L.meta.cap), tp.fills = u32(L.meta.fills), tp.spill_fill = u32(L.meta.sfill), tp.spill_cap = u32(L.meta.scap);
+    tp.toff = u64(L.meta.toff), tp.spill_start = u64(L.meta.sstart);
+
+    // ---- sample
+    VH_HIP(hipMemsetAsync(d_hist, 0, 16 * (uint64_t)T, st));
+    {
+        TimedScope ts("tile_sample");
+        BinPlan p = plan;
+        uint64_t nn = n, bstride = L.bstride;
+        uint32_t s_log2 = tp.s_log2, ntiles = T;
+        void *args[] = {&p, &nn, &s_log2, &ntiles, &bstride, &d_hist, &d_hist2, &d_brange};
+        launch(sample_kernel(nd_f64), (unsigned)L.sblocks, TA_THREADS, 4 * (size_t)T, args);
+    }
+    // scratch of the partition exchange: W regions (or streams) | spill areas | padding
+    auto setup = [&](uint64_t stride, uint64_t stotal) {
+        const uint64_t total = stride * W + stotal + 16;
+        ws.entries.ensure(total * (tp.flags_mode ? 4 : 2));
+        if (nv) ws.values.ensure(total * (tp.vnarrow ? 4 : 8) * nv + 64);
+        tp.wg_stride = stride;
+        tp.spill_base = stride * W;
+        tp.entries = ws.entries.ptr;
+        if (L.stream_layout) {
+            tp.stream = 1;
+            tp.ncw = (uint32_t)L.ncw;
+            ws.tab.ensure((uint64_t)W * (T + 1) * L.ncw * 4 + 256);
+            tp.tab = ws.tab.as<uint32_t>();
         }
+        for (int s = 0; s < nv; s++)
+            tp.values[s] = tp.vnarrow ? reinterpret_cast<double *>(ws.values.as<uint32_t>() + (uint64_t)s * total)
+                                       : ws.values.as<double>() + (uint64_t)s * total;
+        VH_HIP(hipMemsetAsync(tp.spill_fill, 0, 4 * (uint64_t)T, st));
+    };
+    auto launch_pass_a = [&]() {
+        TimedScope ts(tpl.a.scope());
+        BinPlan p = plan;
+        uint64_t nn = n;
+        void *args[] = {&p, &fa, &tp, &nn};
+        launch(kernel_a, W, TA_THREADS, tpl.lds_a, args);
+    };
+    // the sample comes back and the plan goes out through a page-locked block (pageable
+    // copies are staged by the runtime, each one a host wait): [download | upload]; reuse is
+    // safe because every call waits on the stream for its download before writing the block
+    thread_local PinnedBuf tstage;
+    thread_local hipEvent_t sample_ev = nullptr;
+    if (!sample_ev) VH_HIP(hipEventCreateWithFlags(&sample_ev, hipEventDisableTiming));
+    const uint64_t dl_bytes = (16 * (uint64_t)T + 8 * L.sblocks + 255) & ~uint64_t(255);
+    tstage.ensure(dl_bytes + 24 * (uint64_t)T + sizeof(WorkUnit) * L.max_units + 1024);
+    VH_HIP(hipMemcpyAsync(tstage.ptr, d_hist, 16 * (uint64_t)T, hipMemcpyDeviceToHost, st));
+    VH_HIP(hipMemcpyAsync(tstage.as<char>() + 16 * (uint64_t)T, d_brange, 8 * L.sblocks, hipMemcpyDeviceToHost, st));
+    VH_HIP(hipEventRecord(sample_ev, st));
+    // stream layout: the streams are sized exactly without the sample (it only plans pass B),
+    // so pass A is queued right behind the sample's read-back and the host plans pass B while
+    // pass A runs (no host round trip between the two kernels)
+    if (L.stream_layout) {
+        setup(L.stream_stride, 0);
+        launch_pass_a();
+    }
+    VH_HIP(hipEventSynchronize(sample_ev));
+    const uint64_t *hist = tstage.as<uint64_t>();
+    const uint32_t *brange = reinterpret_cast<const uint32_t *>(tstage.as<char>() + 16 * (uint64_t)T);
+    TileRegions reg;
+    if (!size_regions(tpl, L, n, hist, brange, reg)) return false;
+    std::vector<WorkUnit> units;
+    plan_units(tpl, L, n, cu_count(), hist, reg.sampled, units);
+    if (!L.stream_layout) setup(reg.stride, reg.stotal);
+    char *upl = tstage.as<char>() + dl_bytes;  // upload region: cap | toff | sstart | scap | units
+    auto upload = [&](uint64_t meta_off, const void *src, uint64_t bytes) {
+        memcpy(upl, src, bytes);
+        VH_HIP(hipMemcpyAsync(mb + meta_off, upl, bytes, hipMemcpyHostToDevice, st));
+        upl += (bytes + 15) & ~uint64_t(15);
+    };
+    upload(L.meta.cap, reg.cap.data(), 4 * (uint64_t)T);
+    upload(L.meta.toff, reg.toff.data(), 8 * (uint64_t)T);
+    upload(L.meta.sstart, reg.sstart.data(), 8 * (uint64_t)T);
+    upload(L.meta.scap, reg.scap.data(), 4 * (uint64_t)T);
+    if (!units.empty()) upload(L.meta.units, units.data(), sizeof(WorkUnit) * units.size());
+    // ---- pass A (launched before the sample came back in the stream layout)
+    if (!L.stream_layout) launch_pass_a();
+    // ---- pass B
+    TimedScope ts("tile_reduce");
+    // min / max: native-atomic scratch in the LDS cell form, merged after pass B (past 1 GiB
+    // of scratch the flush takes the typed CAS into the grid instead)
+    auto mm_size = [&](const FusedAgg &a) { return ((cells * (mm_cell32(a.dtype) ? 4 : 8)) + 255) & ~uint64_t(255); };
+    uint64_t mm_bytes = 0;
+    for (int k = 0; k < fa.na; k++)
+        if (is_minmax(fa.a[k].kind)) mm_bytes += mm_size(fa.a[k]);
+    if (tpl.b.mm && mm_bytes <= (1ull << 30)) {
+        ws.mmtmp.ensure(mm_bytes + 256);
+        uint64_t off = 0;
+        for (int k = 0; k < fa.na; k++) {
+            if (!is_minmax(fa.a[k].kind)) continue;
+            tp.mmtmp[k] = ws.mmtmp.as<char>() + off;
+            off += mm_size(fa.a[k]);
+            hipLaunchKernelGGL(k_mm_fill, dim3(blocks_for(cells, 256, 8)), dim3(256), 0, st, tp.mmtmp[k], cells,
+                               fa.a[k].dtype, (int)(fa.a[k].kind == VH_AGG_MAX));
+            VH_HIP(hipGetLastError());
+        }
+    }
+    void *args_b[] = {&fa, &tp, &d_units};
+    launch(kernel_b, (unsigned)units.size(), TB_THREADS, tpl.lds_b, args_b);
+    for (int k = 0; k < fa.na; k++) {
+        if (!tp.mmtmp[k]) continue;
+        hipLaunchKernelGGL(k_mm_merge, dim3(blocks_for(cells, 256, 8)), dim3(256), 0, st, fa.a[k].grid, tp.mmtmp[k], cells,
+                           fa.a[k].dtype, (int)(fa.a[k].kind == VH_AGG_MAX));
+        VH_HIP(hipGetLastError());
     }
     return true;
+}
+
+// A plan whose aggregators all carry the same keep mask (a selection / filter) and whose
+// binners have none: the fast pass A applies the mask per row (MK kernels) and the rest of
+// the plan runs as unmasked -- counts of every kept row, no flag entries.  Only when a fast
+// kernel takes the plan; otherwise the masks go to the generic pass A as before.  (C2 with a
+// selection: generic pass A 12.0 ms, profiles/r06_mask.txt.)  VH_TILE_ROWMASK=0: off.
+static bool try_tiled_impl(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64) {
+    const uint8_t *m = fa_in.na > 0 ? fa_in.a[0].mask : nullptr;
+    for (int k = 1; k < fa_in.na && m; k++)
+        if (fa_in.a[k].mask != m) m = nullptr;
+    for (int d = 0; d < plan.nb && m; d++)
+        if (plan.b[d].mask) m = nullptr;
+    const TileSwitches sw = read_switches();
+    if (m && sw.rowmask) {
+        FusedAggs f2 = fa_in;
+        for (int k = 0; k < f2.na; k++) f2.a[k].mask = nullptr;
+        if (try_tiled_core(plan, f2, n, cells, nd_f64, m, sw)) return true;
+    }
+    return try_tiled_core(plan, fa_in, n, cells, nd_f64, nullptr, sw);
 }
 
 bool try_tiled(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64, Workspace &ws) {
@@ -2409,589 +2338,6 @@ bool try_tiled(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t
         return true;
     }
     return try_tiled_impl(plan, fa_in, n, cells, nd_f64);
-}
-
-// Partition scratch shared by every grid of a device: a 1e9-row count+sum needs ~10 GB of
-// regions, which a per-grid buffer would hipMalloc/hipFree for every query (a grid lives
-// for one query).  Held under the device's lock while a bin is enqueued; reuse is ordered
-// by the library stream.
-struct TileScratch {
-    std::mutex mu;
-    DevBuf entries, values, meta, mmtmp, tab;
-};
-
-static bool getenv_flag_off(const char *name) {  // NAME=0 turns a default-on path off (A/B runs)
-    const char *e = getenv(name);
-    return e && atoi(e) == 0;
-}
-static TileScratch &tile_scratch() {
-    static std::mutex g;
-    static std::map<int, std::unique_ptr<TileScratch>> m;
-    std::lock_guard<std::mutex> lk(g);
-    auto &p = m[current_device()];
-    if (!p) p = std::make_unique<TileScratch>();
-    return *p;
-}
-
-static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64,
-                           const uint8_t *rowmask);
-
-// A plan whose aggregators all carry the same keep mask (a selection / filter) and whose
-// binners have none: the fast pass A applies the mask per row (MK kernels) and the rest of
-// the plan runs as unmasked -- counts of every kept row, no flag entries.  Only when a fast
-// kernel takes the plan; otherwise the masks go to the generic pass A as before.  (C2 with a
-// selection: generic pass A 12.0 ms, profiles/r06_mask.txt.)  VH_TILE_ROWMASK=0: off.
-static bool try_tiled_impl(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64) {
-    const uint8_t *m = fa_in.na > 0 ? fa_in.a[0].mask : nullptr;
-    for (int k = 1; k < fa_in.na && m; k++)
-        if (fa_in.a[k].mask != m) m = nullptr;
-    for (int d = 0; d < plan.nb && m; d++)
-        if (plan.b[d].mask) m = nullptr;
-    if (m && !getenv_flag_off("VH_TILE_ROWMASK")) {
-        FusedAggs f2 = fa_in;
-        for (int k = 0; k < f2.na; k++) f2.a[k].mask = nullptr;
-        if (try_tiled_core(plan, f2, n, cells, nd_f64, m)) return true;
-    }
-    return try_tiled_core(plan, fa_in, n, cells, nd_f64, nullptr);
-}
-
-static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64,
-                           const uint8_t *rowmask) {
-    TileScratch &ws = tile_scratch();
-    std::lock_guard<std::mutex> ws_lock(ws.mu);
-    TileParams tp{};
-    tp.rowmask = rowmask;
-#ifdef VH_ABLATION
-    if (const char *dbg = getenv("VH_TILE_DEBUG")) tp.debug = (uint32_t)atoi(dbg);
-#endif
-    // carried values: one slot per distinct value column (sum / min / max of one column share
-    // it: same data, mask, dtype and integer-sum encoding); counts keyed on a matching value
-    int nv = 0;
-    for (int k = 0; k < fa_in.na; k++) {
-        tp.val_slot[k] = -1;
-        tp.cnt_slot[k] = CNT_ALWAYS;
-        if (fa_in.a[k].kind == VH_AGG_COUNT) continue;
-        for (int j = 0; j < k && tp.val_slot[k] < 0; j++)
-            if (tp.val_slot[j] >= 0 && same_value_slot(fa_in.a[j], fa_in.a[k])) tp.val_slot[k] = tp.val_slot[j];
-        if (tp.val_slot[k] < 0) tp.val_slot[k] = nv++;
-    }
-    if (nv > 2) return false;
-    bool flags_mode = false;
-    for (int k = 0; k < fa_in.na; k++) {
-        const FusedAgg &a = fa_in.a[k];
-        if (a.kind != VH_AGG_COUNT || (!a.data && !a.mask)) continue;
-        if (!a.mask && a.dtype != VH_F64 && a.dtype != VH_F32) continue;  // integers: never NaN
-        tp.cnt_slot[k] = CNT_FLAG;
-        for (int j = 0; j < fa_in.na; j++)
-            if (fa_in.a[j].kind != VH_AGG_COUNT && fa_in.a[j].data == a.data && fa_in.a[j].mask == a.mask && a.data &&
-                !fa_in.a[j].vint)
-                tp.cnt_slot[k] = tp.val_slot[j];
-        if (tp.cnt_slot[k] == CNT_FLAG) flags_mode = true;
-    }
-    if (flags_mode)
-        for (int k = 0; k < fa_in.na; k++)
-            if (fa_in.a[k].kind == VH_AGG_COUNT) tp.cnt_slot[k] = CNT_FLAG;
-    // LDS bytes per cell of pass B: u32 counts, 8-byte sums, min / max 4 or 8 (mm_cell32)
-    auto cell_bytes = [](const FusedAgg &a) -> uint64_t {
-        return a.kind == VH_AGG_COUNT || (is_minmax(a.kind) && mm_cell32(a.dtype)) ? 4 : 8;
-    };
-    uint64_t per_cell = 0;
-    for (int k = 0; k < fa_in.na; k++) per_cell += cell_bytes(fa_in.a[k]);
-    // pass B's LDS tile: 96 KB for count / sum plans; wider cells (min / max / moment) get up
-    // to 128 KB so their tiles keep 4096 cells (fewer tiles: longer pass-A runs per region)
-    const uint64_t budget = per_cell > 12 ? std::max<uint64_t>(TILE_LDS_BUDGET, 128 * 1024) : TILE_LDS_BUDGET;
-    uint32_t s_log2 = 0;
-    while (s_log2 < 16 && ((uint64_t)2 << s_log2) * per_cell <= budget) s_log2++;
-    const uint64_t S = 1ull << s_log2;
-    const uint64_t T64 = (cells + S - 1) / S;
-    if (T64 > TILE_MAX_TILES || T64 < 2) return false;
-    const uint32_t T = (uint32_t)T64;
-
-    FusedAggs fa = fa_in;
-    uint64_t off = 0;
-    for (int k = 0; k < fa.na; k++) {
-        off = (off + 7) & ~uint64_t(7);
-        fa.a[k].lds_off = (uint32_t)off;
-        off += S * cell_bytes(fa.a[k]);
-    }
-    const uint64_t lds_b = (off + 15) & ~uint64_t(15);
-    fa.lds_words = (uint32_t)(lds_b / 4);
-    hipStream_t st = stream();
-
-    // ---- sample
-    // the fast pass A: native f64 binners and sums, no masks, 16-byte aligned columns
-    bool fast = nd_f64 > 0 && !flags_mode;
-    // generic pass A flavour: -1 = a set-ordinal binner (per-row form), 0 = hoisted dispatch
-    bool has_set = false;
-    for (int d = 0; d < plan.nb; d++) has_set = has_set || plan.b[d].kind == 2;
-    for (int d = 0; d < plan.nb && fast; d++) fast = !plan.b[d].mask && aligned16(plan.b[d].data);
-    for (int k = 0; k < fa.na; k++) {
-        if (fa.a[k].mask) fast = false;
-        if (fa.a[k].kind != VH_AGG_COUNT) {
-            tp.vdata[tp.val_slot[k]] = fa.a[k].data;
-            fast = fast && fa.a[k].data && fa.a[k].dtype == VH_F64 && aligned16(fa.a[k].data);
-        }
-        if (fa.a[k].kind == VH_AGG_COUNT && fa.a[k].data && fa.a[k].dtype != VH_F64) fast = false;
-    }
-    // the fast float32 pass A (k_tile_scatter_f64<ND, NV, SB, float>): native float32 scalar
-    // binners without masks, float32 sums and counts (of every row, or keyed on a summed
-    // column), no aggregator masks, 8-byte aligned columns, n even (row pairs).  It replaces
-    // the generic pass A's per-dimension dtype dispatch, whose loads wait at every switch join
-    // (C2 on float32 columns: 11.3 ms generic pass A, profiles/r06_f32.txt)
-    // Mixed plans take the same kernel with a second value-pair array (modes 6 / 7 below).
-    int nd_f32 = 0, mix_mode = 0;  // 5: float32 / float32, 6: float32 binners + float64 values, 7: the reverse
-    if (!fast && !flags_mode && n % 2 == 0 && plan.nb >= 1 && plan.nb <= 3 && !getenv_flag_off("VH_TILE_F32")) {
-        bool ok = true;
-        int bt = -1, vt = -1;
-        for (int d = 0; d < plan.nb; d++) {
-            const BinnerDev &b = plan.b[d];
-            const int dt = b.dtype;
-            ok = ok && b.kind == 0 && (dt == VH_F32 || dt == VH_F64 || dt == VH_I32 || dt == VH_I64) && (bt < 0 || dt == bt) &&
-                 !b.flip && !b.mask && (dt == VH_F64 || dt == VH_I64 ? aligned16(b.data) : aligned8(b.data));
-            bt = dt;
-        }
-        for (int k = 0; k < fa.na; k++) {
-            const FusedAgg &a = fa.a[k];
-            ok = ok && !a.mask;
-            if (a.kind == VH_AGG_COUNT) continue;
-            ok = ok && a.kind == VH_AGG_SUM && a.data && (a.dtype == VH_F32 || a.dtype == VH_F64) && (vt < 0 || a.dtype == vt) &&
-                 (a.dtype == VH_F64 ? aligned16(a.data) : aligned8(a.data));
-            vt = a.dtype;
-        }
-        if (vt < 0) vt = bt;
-        for (int k = 0; k < fa.na; k++)  // counts of a column: the summed one (flags_mode otherwise)
-            if (fa.a[k].kind == VH_AGG_COUNT && fa.a[k].data) ok = ok && fa.a[k].dtype == vt;
-        if (vt == VH_I32 || vt == VH_I64) vt = VH_F64;  // integer binners, no values: the float64 form
-        if (ok) {
-            if (bt == VH_I32 || bt == VH_I64)  // integer binners (1- and 2-d): 8 / 9 int32, 10 / 11 int64
-                mix_mode = plan.nb > 2 ? 0 : (bt == VH_I32 ? 8 : 10) + (vt == VH_F32 ? 1 : 0);
-            else
-                mix_mode = bt == VH_F32 ? (vt == VH_F32 ? 5 : 6) : (vt == VH_F32 ? 7 : 0);
-            if (mix_mode) nd_f32 = plan.nb;
-        }
-    }
-    const bool ord = !fast && n % 2 == 0 && ord_fast_ok(plan, fa);
-    tp.vdt[0] = tp.vdt[1] = VH_F64;
-    if (ord) for (int k = 0; k < fa.na; k++)
-        if (fa.a[k].kind != VH_AGG_COUNT) {
-            tp.vdata[tp.val_slot[k]] = fa.a[k].data;
-            tp.vdt[tp.val_slot[k]] = fa.a[k].dtype;
-        }
-    // 4-byte value slots when every summed column of a generic plan is <= 4 bytes (exact)
-    bool vnarrow = fa.generic_vals && nv > 0 && !fast && !getenv_flag_off("VH_TILE_NARROW");
-    uint32_t vfloat = 0, vsigned = 0;
-    for (int k = 0; k < fa.na && vnarrow; k++) {
-        if (fa.a[k].kind == VH_AGG_COUNT) continue;
-        const int dt = fa.a[k].dtype, s = tp.val_slot[k];
-        if (dtype_itemsize(dt) > 4) vnarrow = false;
-        if (dt == VH_F32) vfloat |= 1u << s;
-        if (dt == VH_I32 || dt == VH_I16 || dt == VH_I8) vsigned |= 1u << s;
-    }
-    // fast kernel: several batches per commit when that staging fits the LDS; the ordinal
-    // kernel with narrow slots stages 4-byte values (mode 3); the float32 kernel too (mode 5:
-    // its sums are float32 bits in narrow slots)
-    const bool narrow_ord = ord && vnarrow &&
-                            fast_lds_bytes(nv, T, (uint32_t)(fast_sb_narrow(nv) * TA_BATCH), 4) <= LDS_MAX_BYTES;
-    const bool vf32 = mix_mode == 5 || mix_mode == 7 || mix_mode == 9 || mix_mode == 11;
-    const int sb_mix = vf32 ? fast_sb_narrow(nv) : fast_sb_nd(nv, plan.nb);
-    const bool f32_ok = mix_mode != 0 && (nv == 0 || vnarrow == vf32) &&
-                        fast_lds_bytes(nv, T, (uint32_t)(sb_mix * TA_BATCH), vf32 ? 4 : 8) <= LDS_MAX_BYTES;
-    const int fast_mode = f32_ok ? mix_mode
-                          : !(fast || ord) ? 0
-                          : narrow_ord  ? 3
-                          : fast_lds_bytes(nv, T, (uint32_t)(fast_sb_nd(nv, fast ? nd_f64 : 1) * TA_BATCH)) <= LDS_MAX_BYTES ? 2 : 1;
-    // the scatter kernels' ND: float64 binner dimensions (fast or generic kernels read them as
-    // float64), the float32 / mixed kernels' dimensions only when one of them runs, else the
-    // generic dispatch (0) or the set-ordinal form (-1) -- a float32 plan the fast kernels do
-    // not take must not reach an ND > 0 generic kernel, which would read its columns as float64
-    const int nd_k = nd_f64 > 0 ? nd_f64 : fast_mode >= 5 ? nd_f32 : (has_set ? -1 : 0);
-    // a shared keep mask runs only on the fast f64 / f32 kernels' MK instantiations
-    if (rowmask && !((fast && fast_mode == 2) || fast_mode == 5 ||
-                     (ord && ord_kernel(nv, fast_mode, has_set, tp.vdt[0], tp.vdt[1], true) != nullptr)))
-        return false;
-    // wide stream-out (batch_commit_fast): runs padded to 8 entries, 16-byte region stores;
-    // needs 8 T more staged entries of LDS and tiles below 2^16 - 1 cells (DUMMY_CELL).
-    // VH_TILE_WIDE: bit 0 wide, bit 1 non-temporal cell stores, bit 2 non-temporal value stores
-    const int sb_k = fast_mode >= 5 ? sb_mix : fast_mode == 3 ? fast_sb_narrow(nv) : fast_mode == 2 ? fast_sb_nd(nv, fast ? nd_f64 : 1) : 1;
-    const uint32_t cap0 = (uint32_t)(sb_k * TA_BATCH);
-    const int vbytes = fast_mode == 3 || (fast_mode >= 5 && vf32) ? 4 : 8;
-    uint32_t wide_mode = 7;
-    if (const char *e = getenv("VH_TILE_WIDE")) wide_mode = (uint32_t)atoi(e);
-    const bool wide = (wide_mode & 1) && fast_mode != 0 && !flags_mode && S < DUMMY_CELL &&
-                      fast_lds_bytes(nv, T, cap0 + 8 * T, vbytes) <= LDS_MAX_BYTES;
-    tp.wide = wide ? wide_mode : 0u;
-    tp.lds_cap = wide ? cap0 + 8 * T : cap0;
-    const size_t lds_a = fast_mode != 0 ? fast_lds_bytes(nv, T, tp.lds_cap, vbytes) : scatter_lds_bytes(nv, T);
-    if (lds_a > LDS_MAX_BYTES) return false;  // very many tiles: the global-atomic path
-    int bpc;
-    {
-        static std::mutex mu;
-        static std::map<std::tuple<int, int, int, int, size_t>, int> cache;
-        std::lock_guard<std::mutex> lk(mu);
-        const auto key = std::make_tuple(current_device(), ord ? (has_set ? -3 : -2) - 4 * (tp.vdt[0] + 32 * tp.vdt[1]) : nd_k, nv,
-                                         fast_mode + (rowmask ? 16 : 0), lds_a);
-        auto it = cache.find(key);
-        if (it == cache.end()) {
-            int v = 0;
-            if (ord) {
-                const void *kf = ord_kernel(nv, fast_mode, has_set, tp.vdt[0], tp.vdt[1], rowmask != nullptr);
-                VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kf, TA_THREADS, lds_a));
-            } else {
-                v = nv == 0 ? scatter_blocks_per_cu_nd<0>(nd_k, fast_mode, lds_a, rowmask != nullptr)
-                            : nv == 1 ? scatter_blocks_per_cu_nd<1>(nd_k, fast_mode, lds_a, rowmask != nullptr)
-                                      : scatter_blocks_per_cu_nd<2>(nd_k, fast_mode, lds_a, rowmask != nullptr);
-            }
-            it = cache.emplace(key, v).first;
-        }
-        bpc = it->second;
-    }
-    bpc = std::max(1, std::min(bpc, TA_WG_PER_CU));
-    const uint32_t W = std::min<uint32_t>(1024, (uint32_t)cu_count() * bpc);
-    const uint64_t nb = (n + TA_BATCH - 1) / TA_BATCH;
-    const uint64_t kbat = (nb + W - 1) / W;  // batches per workgroup (at most)
-    const uint64_t rows_per_wg = kbat * TA_BATCH;
-    const uint64_t ncw = (kbat + sb_k - 1) / sb_k;  // commits per workgroup (at most)
-    // stream layout (TileParams::stream): one exactly sized stream per workgroup, no sampled
-    // capacities, spill areas or overflow rows; VH_TILE_STREAM=0 keeps the per-tile regions
-    // count-only plans keep the per-tile regions: their 2-byte entries make a stream segment's
-    // partial lines a large share of pass B's reads (C2 count-only, same-process A/B: pass A
-    // unchanged, pass B 0.8 -> 1.2 ms), while value-carrying plans gain in pass A (C2 count+sum
-    // 7.56 -> 6.93 ms, C3 4.68 -> 4.14 ms; scripts/exp_stream.py, profiles/r06_stream.txt)
-    const bool stream_layout = wide && nv > 0 && !getenv_flag_off("VH_TILE_STREAM") &&
-                               (uint64_t)W * (T + 1) * ncw < (1ull << 31);
-    // stream layout: a pass-B unit walks (workgroup, commit) segments in rounds of
-    // TB_THREADS; at most TB_ROUNDS rounds per unit (a cold tile's single unit would walk all
-    // W x ncw segments in one workgroup while the rest of the chip idles)
-#ifndef VH_TB_ROUNDS
-#define VH_TB_ROUNDS 6
-#endif
-    constexpr uint64_t TB_ROUNDS = VH_TB_ROUNDS;
-    const uint64_t wpu = std::max<uint64_t>(1, (uint64_t)TB_THREADS * TB_ROUNDS / std::max<uint64_t>(ncw, 1));
-    const uint64_t g_min = stream_layout ? (W + wpu - 1) / wpu : 1;
-    // pass-B work units: sum over tiles of max(g_min, ceil(e_t / target)) <= T g_min + 4 cu
-    // (target = n / 4 cu)
-    const uint64_t max_units = (uint64_t)T * g_min + 4 * (uint64_t)cu_count() + 16;
-    DevBuf &meta = ws.meta;
-    const uint64_t meta_bytes = 8 * (uint64_t)T /*hist*/ + 8 * (uint64_t)T /*hist2*/ + 8 * (uint64_t)T /*toff*/ +
-                                8 * (uint64_t)T /*spill_start*/ + 4 * (uint64_t)T /*spill_cap*/ + 4 * (uint64_t)T /*spill_fill*/ +
-                                4 * (uint64_t)T /*cap*/ + 4 * (uint64_t)T * W /*fills*/ + 16 * max_units /*units*/ +
-                                8 * (uint64_t)SAMPLE_BLOCKS /*brange*/ + 256;
-    meta.ensure(meta_bytes);
-    unsigned char *mb = meta.as<unsigned char>();
-    uint64_t *d_hist = reinterpret_cast<uint64_t *>(mb);
-    uint64_t *d_hist2 = d_hist + T;
-    uint64_t *d_toff = d_hist2 + T;
-    uint64_t *d_sstart = d_toff + T;
-    uint32_t *d_scap = reinterpret_cast<uint32_t *>(d_sstart + T);
-    uint32_t *d_sfill = d_scap + T;
-    uint32_t *d_cap = d_sfill + T;
-    uint32_t *d_fills = d_cap + ((T + 3) & ~3u);
-    WorkUnit *d_units = reinterpret_cast<WorkUnit *>(d_fills + (uint64_t)T * W + 4 - ((uint64_t)T * W) % 4);
-    uint32_t *d_brange = reinterpret_cast<uint32_t *>(d_units + max_units);
-    const uint64_t sblocks = std::min<uint64_t>(nb, SAMPLE_BLOCKS);
-    const uint64_t bstride = std::max<uint64_t>(TA_BATCH, (n / sblocks));
-    VH_HIP(hipMemsetAsync(d_hist, 0, 16 * (uint64_t)T, st));
-    {
-        TimedScope ts("tile_sample");
-        const size_t lds = 4 * (size_t)T;
-        switch (nd_f64) {
-        case 1: hipLaunchKernelGGL(k_tile_sample<1>, dim3(sblocks), dim3(TA_THREADS), lds, st, plan, n, s_log2, T, bstride, d_hist, d_hist2, d_brange); break;
-        case 2: hipLaunchKernelGGL(k_tile_sample<2>, dim3(sblocks), dim3(TA_THREADS), lds, st, plan, n, s_log2, T, bstride, d_hist, d_hist2, d_brange); break;
-        case 3: hipLaunchKernelGGL(k_tile_sample<3>, dim3(sblocks), dim3(TA_THREADS), lds, st, plan, n, s_log2, T, bstride, d_hist, d_hist2, d_brange); break;
-        default: hipLaunchKernelGGL(k_tile_sample<0>, dim3(sblocks), dim3(TA_THREADS), lds, st, plan, n, s_log2, T, bstride, d_hist, d_hist2, d_brange);
-        }
-        VH_HIP(hipGetLastError());
-    }
-    // scratch and parameters of the partition exchange (regions: after the sample sized them)
-    auto setup = [&](uint64_t stride, uint64_t stotal) {
-        const uint64_t total = stride * W + stotal + 16;  // regions | spill areas | padding
-        const int ebytes = flags_mode ? 4 : 2;
-        ws.entries.ensure(total * ebytes);
-        if (nv) ws.values.ensure(total * (vnarrow ? 4 : 8) * nv + 64);
-        tp.vnarrow = vnarrow ? 1u : 0u;
-        // the narrow ordinal pass A with two carried columns stores both in values[0], blocked
-        // by 8 entries (values[0] spans both slot arrays; values[1] is unused)
-        tp.vpacked = ((fast_mode == 3 || (fast_mode >= 5 && vf32)) && nv == 2 && !flags_mode && !getenv_flag_off("VH_TILE_PACK")) ? 1u : 0u;
-        tp.vfloat = vfloat;
-        tp.vsigned = vsigned;
-        tp.s_log2 = s_log2;
-        tp.ntiles = T;
-        tp.flags_mode = flags_mode ? 1 : 0;
-        tp.nvals = nv;
-        tp.cells = cells;
-        tp.W = W;
-        tp.rows_per_wg = rows_per_wg;
-        tp.wg_stride = stride;
-        tp.cap = d_cap;
-        tp.toff = d_toff;
-        tp.fills = d_fills;
-        tp.spill_fill = d_sfill;
-        tp.spill_cap = d_scap;
-        tp.spill_start = d_sstart;
-        tp.spill_base = stride * W;
-        tp.entries = ws.entries.ptr;
-        if (stream_layout) {
-            tp.stream = 1;
-            tp.ncw = (uint32_t)ncw;
-            ws.tab.ensure((uint64_t)W * (T + 1) * ncw * 4 + 256);
-            tp.tab = ws.tab.as<uint32_t>();
-        }
-        for (int s = 0; s < nv; s++)
-            tp.values[s] = vnarrow ? reinterpret_cast<double *>(ws.values.as<uint32_t>() + (uint64_t)s * total)
-                                   : ws.values.as<double>() + (uint64_t)s * total;
-        VH_HIP(hipMemsetAsync(d_sfill, 0, 4 * (uint64_t)T, st));
-    };
-    bool a_launched = false;
-    auto launch_pass_a = [&]() {
-        TimedScope ts(fast ? "tile_scatter_f64" : fast_mode == 5 ? "tile_scatter_f32" : fast_mode >= 8 ? "tile_scatter_int" : fast_mode >= 6 ? "tile_scatter_mixed" : ord ? (has_set ? "tile_scatter_set" : "tile_scatter_ord") : "tile_scatter");
-        const size_t lds = lds_a;
-        if (ord) {
-            const void *kf = ord_kernel(nv, fast_mode, has_set, tp.vdt[0], tp.vdt[1], rowmask != nullptr);
-            void *args[] = {(void *)&plan, (void *)&fa, (void *)&tp, (void *)&n};
-            VH_HIP(hipLaunchKernel(kf, dim3(W), dim3(TA_THREADS), args, lds, st));
-        } else {
-            switch (nv) {
-            case 0: launch_scatter_nd<0>(nd_k, fast_mode, W, lds, plan, fa, tp, n); break;
-            case 1: launch_scatter_nd<1>(nd_k, fast_mode, W, lds, plan, fa, tp, n); break;
-            default: launch_scatter_nd<2>(nd_k, fast_mode, W, lds, plan, fa, tp, n);
-            }
-        }
-        VH_HIP(hipGetLastError());
-        a_launched = true;
-    };
-    // the sample comes back and the plan goes out through a page-locked block (pageable
-    // copies are staged by the runtime, each one a host wait): [download | upload]; reuse is
-    // safe because every call waits on the stream for its download before writing the block
-    thread_local PinnedBuf tstage;
-    thread_local hipEvent_t sample_ev = nullptr;
-    if (!sample_ev) VH_HIP(hipEventCreateWithFlags(&sample_ev, hipEventDisableTiming));
-    const uint64_t dl_bytes = (16 * (uint64_t)T + 8 * sblocks + 255) & ~uint64_t(255);
-    tstage.ensure(dl_bytes + 24 * (uint64_t)T + sizeof(WorkUnit) * max_units + 1024);
-    VH_HIP(hipMemcpyAsync(tstage.ptr, d_hist, 16 * (uint64_t)T, hipMemcpyDeviceToHost, st));
-    VH_HIP(hipMemcpyAsync(tstage.as<char>() + 16 * (uint64_t)T, d_brange, 8 * sblocks, hipMemcpyDeviceToHost, st));
-    VH_HIP(hipEventRecord(sample_ev, st));
-    // stream layout: the streams are sized exactly without the sample (it only plans pass B),
-    // so pass A is queued right behind the sample's read-back and the host plans pass B while
-    // pass A runs (no host round trip between the two kernels)
-    if (stream_layout) {
-        uint64_t sstride = (rows_per_wg + 7 * ncw * T + 8 + 7) & ~uint64_t(7);
-        if (const char *e = getenv("VH_TILE_WGPAD")) sstride += ((uint64_t)strtoull(e, nullptr, 10) + 7) & ~uint64_t(7);
-        setup(sstride, 0);
-        launch_pass_a();
-    }
-    VH_HIP(hipEventSynchronize(sample_ev));
-    const uint64_t *hist = tstage.as<uint64_t>();
-    const uint32_t *brange = reinterpret_cast<const uint32_t *>(tstage.as<char>() + 16 * (uint64_t)T);
-    // sample blocks whose tile ranges follow each other (a column sorted, up or down, along
-    // the grid index): each workgroup's evenly spaced batches then meet a tile floor or ceil
-    // of K p_t times, and p_t is exact to a block
-    uint64_t up = 0, down = 0;
-    for (uint64_t b = 0; b + 1 < sblocks; b++) {
-        up += brange[2 * b + 1] > brange[2 * b + 2];    // block b ends past block b + 1's start
-        down += brange[2 * b] < brange[2 * b + 3];
-    }
-    const bool monotone = sblocks > 8 && std::min(up, down) * 100 <= sblocks;
-    uint64_t sampled = 0;
-    for (uint32_t t = 0; t < T; t++) sampled += hist[t];
-    if (!sampled) return false;
-
-    // ---- region capacities per workgroup.  Pass-A workgroup w takes batches w, w + W,
-    // w + 2W, ... (TA_BATCH rows each), so every workgroup's rows are spread over the whole
-    // row range and its tile distribution is the global one whatever the row order (a sorted
-    // or clustered column would otherwise send a contiguous range's rows to a few tiles and
-    // overflow their regions).  Regions are sized for shuffled rows (Poisson spread); a
-    // workgroup's rows past its region go to the tile's spill area, sized from the spread the
-    // sample measures per batch-sized block (clustered rows: each block all in or all out of
-    // a tile) -- half the tile's expected rows when the rows are clustered.
-    // wide stream-out: up to 7 padding entries per (workgroup, tile) and commit
-    const uint64_t pad_wg = wide ? 7 * ncw : 0;
-    std::vector<uint32_t> cap(T), scap(T);
-    std::vector<uint64_t> toff(T), sstart(T);
-    uint64_t stride = 0, stotal = 0;
-    for (uint32_t t = 0; t < T && stream_layout; t++) cap[t] = scap[t] = 0, toff[t] = sstart[t] = 0;
-    const double blocks = (double)sblocks;  // every sample block is TA_BATCH rows, like a batch
-    // clustered rows (block variance well above the Poisson value: each sample block all in
-    // or all out of a tile) anywhere in the sample
-    bool any_clustered = false;
-    for (uint32_t t = 0; t < T; t++) {
-        const double m = (double)hist[t] / blocks, var_b = std::max(0.0, (double)hist[T + t] / blocks - m * m);
-        any_clustered = any_clustered || var_b > 4.0 * m + 1.0;
-    }
-    for (uint32_t t = 0; t < T && !stream_layout; t++) {
-        const double p = (double)hist[t] / (double)sampled, e = (double)rows_per_wg * p;
-        const double m = (double)hist[t] / blocks, var_b = std::max(0.0, (double)hist[T + t] / blocks - m * m);
-        const bool clustered = var_b > 4.0 * m + 1.0;
-        // a clustered tile gets one batch of slack: a workgroup's evenly spaced batches meet a
-        // sorted column's tile floor or ceil of K p_t times
-        uint64_t c = (uint64_t)(e * 1.04 + 6.0 * std::sqrt(e + 1.0)) + 32 + (clustered ? TA_BATCH : 0) + pad_wg;
-        c = std::min<uint64_t>((c + 7) & ~uint64_t(7), rows_per_wg + pad_wg + 8);
-        cap[t] = (uint32_t)c;
-        toff[t] = stride;
-        stride += c;
-        uint64_t sc = (uint64_t)(0.02 * (double)n * p) + TA_BATCH;
-        // a tile the sample missed between two clustered sample blocks holds at most the rows
-        // between them
-        if (any_clustered && hist[t] == 0) sc = std::min<uint64_t>(n, bstride) + TA_BATCH;
-        if (clustered && !monotone) {
-            // whole batches land in a tile: a workgroup's batches in tile t ~ Poisson(K p_hi)
-            // (p_hi: p plus two standard errors of a block sample); spill = the expected
-            // excess over the region, x 2, for all workgroups (<= 1.25 n p_hi)
-            const double p_hi = std::min(1.0, p + 2.0 * std::sqrt(p * (1.0 - p) / blocks));
-            const double lam = (double)kbat * p_hi;
-            double excess = 0.0, pk = std::exp(-lam);
-            for (uint64_t x = 0; x <= kbat && (double)x <= lam + 12.0 * std::sqrt(lam) + 12.0; x++) {
-                if (x) pk *= lam / (double)x;
-                excess += pk * std::max(0.0, (double)x * TA_BATCH - (double)c);
-            }
-            sc = (uint64_t)std::min(1.25 * (double)n * p_hi, 2.0 * (double)W * excess) + 4 * TA_BATCH;
-        }
-        if (wide) sc += sc / 4 + 8 * (uint64_t)W;  // padding of the spilled runs
-        scap[t] = (uint32_t)std::min<uint64_t>((sc + 7) & ~uint64_t(7), (uint64_t)n + 8 * (uint64_t)W + 8);
-        sstart[t] = stotal;
-        stotal += scap[t];
-    }
-    // pass A keeps region positions in u32 (destination | overflow bit), spill entries below
-    // DEST_SPILL
-    if (stride + rows_per_wg + pad_wg >= (uint64_t)DEST_SPILL) return false;
-    if (stotal >= (uint64_t)DEST_SPILL) {  // very large launches: shrink the spill areas
-        const double f = (double)(DEST_SPILL - 8 * (uint64_t)T) / (double)stotal;
-        stotal = 0;
-        for (uint32_t t = 0; t < T; t++) {
-            scap[t] = (uint32_t)(((uint64_t)(scap[t] * f)) & ~uint64_t(7));
-            sstart[t] = stotal;
-            stotal += scap[t];
-        }
-    }
-    if (!stream_layout) setup(stride, stotal);
-    char *upl = tstage.as<char>() + dl_bytes;  // upload region: cap | toff | sstart | scap | units
-    auto upload = [&](void *dst, const void *src, uint64_t bytes) {
-        memcpy(upl, src, bytes);
-        VH_HIP(hipMemcpyAsync(dst, upl, bytes, hipMemcpyHostToDevice, st));
-        upl += (bytes + 15) & ~uint64_t(15);
-    };
-    upload(d_cap, cap.data(), 4 * (uint64_t)T);
-    upload(d_toff, toff.data(), 8 * (uint64_t)T);
-    upload(d_sstart, sstart.data(), 8 * (uint64_t)T);
-    upload(d_scap, scap.data(), 4 * (uint64_t)T);
-
-    // ---- pass B work units: tiles split over ranges of pass-A workgroups by expected size;
-    // unit k of g of a tile also reads slice k of g of the tile's spill area
-    std::vector<WorkUnit> units;
-    const double target = std::max(1.0, (double)n / ((double)cu_count() * 4));
-    std::vector<double> unit_rows;
-    for (uint32_t t = 0; t < T; t++) {
-        const double e = (double)n * (double)hist[t] / (double)sampled;
-        uint32_t g = (uint32_t)std::min<double>(W, std::max((double)g_min, std::ceil(e / target)));
-        for (uint32_t k = 0; k < g; k++) {
-            units.push_back({t, (uint32_t)((uint64_t)W * k / g), (uint32_t)((uint64_t)W * (k + 1) / g), k | (g << 16)});
-            unit_rows.push_back(e / g);
-        }
-    }
-    if (stream_layout) {
-        // largest units first (they start before the small ones fill the chip's tail)
-        std::vector<uint32_t> ord(units.size());
-        for (uint32_t i = 0; i < ord.size(); i++) ord[i] = i;
-        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return unit_rows[a] > unit_rows[b]; });
-        std::vector<WorkUnit> sorted(units.size());
-        for (uint32_t i = 0; i < ord.size(); i++) sorted[i] = units[ord[i]];
-        units.swap(sorted);
-    }
-    if (units.size() > max_units) fail(VH_ERR_RUNTIME, "tiled binning: work-unit table overflow");
-    if (!units.empty()) upload(d_units, units.data(), sizeof(WorkUnit) * units.size());
-
-    // ---- pass A (launched before the sample comes back in the stream layout)
-    if (!a_launched) launch_pass_a();
-    // ---- pass B
-    {
-        TimedScope ts("tile_reduce");
-        // MM: min / max cells or moment terms in pass B (the extended run form; a moment
-        // other than 2 takes the per-entry form)
-        bool mm = false;
-        for (int k = 0; k < fa.na; k++) {
-            const FusedAgg &a = fa.a[k];
-            mm = mm || is_minmax(a.kind) || a.kind == VH_AGG_SUM_MOMENT;
-            if (a.kind == VH_AGG_SUM_MOMENT && a.moment != 2) tp.mgeneric = 1;
-            if (is_minmax(a.kind)) tp.mmk |= 1u << k;
-        }
-        // the branch-light form: one float64 value slot (8-byte), at most one count, sum, min and
-        // max of it, count(*) or the count of its non-NaN values
-        {
-            bool simple = mm && !tp.mgeneric && nv == 1 && !vnarrow && !flags_mode;
-            int off[4] = {-1, -1, -1, -1};
-            uint32_t cnn = 0;
-            for (int k = 0; k < fa.na && simple; k++) {
-                const FusedAgg &a = fa.a[k];
-                const int slot = a.kind == VH_AGG_COUNT ? -1 : tp.val_slot[k];
-                int r = -1;
-                if (a.kind == VH_AGG_COUNT) {
-                    r = 0;
-                    if (tp.cnt_slot[k] == 0) cnn = 1;
-                    else if (tp.cnt_slot[k] != CNT_ALWAYS) simple = false;
-                } else if (a.kind == VH_AGG_SUM && !a.vint && a.dtype == VH_F64 && slot == 0) r = 1;
-                else if (a.kind == VH_AGG_MIN && a.dtype == VH_F64 && slot == 0) r = 2;
-                else if (a.kind == VH_AGG_MAX && a.dtype == VH_F64 && slot == 0) r = 3;
-                else simple = false;
-                if (r >= 0) {
-                    if (off[r] >= 0) simple = false;  // two of one kind
-                    else off[r] = (int)a.lds_off;
-                }
-            }
-            tp.mm_simple = simple ? 1u : 0u;
-            tp.mm_cnt_nn = cnn;
-            for (int r = 0; r < 4; r++) tp.mm_off[r] = off[r];
-        }
-        uint64_t mm_bytes = 0;
-        for (int k = 0; k < fa.na; k++)
-            if (is_minmax(fa.a[k].kind)) mm_bytes += ((cells * (mm_cell32(fa.a[k].dtype) ? 4 : 8)) + 255) & ~uint64_t(255);
-        if (mm && mm_bytes <= (1ull << 30)) {
-            // min / max: native-atomic scratch in the LDS cell form, merged after pass B (past
-            // 1 GiB of scratch the flush takes the typed CAS into the grid instead)
-            uint64_t off = 0;
-            ws.mmtmp.ensure(mm_bytes + 256);
-            off = 0;
-            for (int k = 0; k < fa.na; k++) {
-                if (!is_minmax(fa.a[k].kind)) continue;
-                tp.mmtmp[k] = ws.mmtmp.as<char>() + off;
-                off += ((cells * (mm_cell32(fa.a[k].dtype) ? 4 : 8)) + 255) & ~uint64_t(255);
-                hipLaunchKernelGGL(k_mm_fill, dim3(blocks_for(cells, 256, 8)), dim3(256), 0, st, tp.mmtmp[k], cells,
-                                   fa.a[k].dtype, (int)(fa.a[k].kind == VH_AGG_MAX));
-                VH_HIP(hipGetLastError());
-            }
-        }
-        const unsigned g = (unsigned)units.size();
-#define VH_TB(NV_, NAR_)                                                                                      \
-    do {                                                                                                      \
-        if (mm && tp.mgeneric) hipLaunchKernelGGL((k_tile_reduce<NV_, NAR_, true, false, true>), dim3(g), dim3(TB_THREADS), lds_b, st, fa, tp, d_units); \
-        else if (mm) hipLaunchKernelGGL((k_tile_reduce<NV_, NAR_, true>), dim3(g), dim3(TB_THREADS), lds_b, st, fa, tp, d_units); \
-        else hipLaunchKernelGGL((k_tile_reduce<NV_, NAR_, false>), dim3(g), dim3(TB_THREADS), lds_b, st, fa, tp, d_units); \
-    } while (0)
-        switch (nv) {
-        case 0: hipLaunchKernelGGL((k_tile_reduce<0, false, false>), dim3(g), dim3(TB_THREADS), lds_b, st, fa, tp, d_units); break;
-        case 1:
-            if (vnarrow) VH_TB(1, true);
-            else VH_TB(1, false);
-            break;
-        default:
-            if (tp.vpacked) {
-                if (mm && tp.mgeneric) hipLaunchKernelGGL((k_tile_reduce<2, true, true, true, true>), dim3(g), dim3(TB_THREADS), lds_b, st, fa, tp, d_units);
-                else if (mm) hipLaunchKernelGGL((k_tile_reduce<2, true, true, true>), dim3(g), dim3(TB_THREADS), lds_b, st, fa, tp, d_units);
-                else hipLaunchKernelGGL((k_tile_reduce<2, true, false, true>), dim3(g), dim3(TB_THREADS), lds_b, st, fa, tp, d_units);
-            } else if (vnarrow) {
-                VH_TB(2, true);
-            } else {
-                VH_TB(2, false);
-            }
-        }
-#undef VH_TB
-        VH_HIP(hipGetLastError());
-        for (int k = 0; k < fa.na; k++) {
-            if (!tp.mmtmp[k]) continue;
-            hipLaunchKernelGGL(k_mm_merge, dim3(blocks_for(cells, 256, 8)), dim3(256), 0, st, fa.a[k].grid, tp.mmtmp[k], cells,
-                               fa.a[k].dtype, (int)(fa.a[k].kind == VH_AGG_MAX));
-            VH_HIP(hipGetLastError());
-        }
-    }
-    return true;
 }
 
 uint64_t stat_tile_overflow(bool reset) {
