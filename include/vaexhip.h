@@ -177,6 +177,14 @@ int vh_agg_download_order(vh_agg *agg, void *host, uint64_t bytes); /* AggFirst 
  * begin ({0, -1, -1} when none) -- the occupied range of a dense groupby's count(*) grid, found
  * on the device (groupby.py:484-533 keeps the cells with count > 0). */
 int vh_agg_occupancy(vh_agg *agg, uint64_t begin, uint64_t end, int64_t *out3);
+/* percentile finish of an AggCount grid whose last binner is the percentile axis
+ * (dataframe.py:1419-1555 finish + vaexfast.cpp:1574-1628 grid_find_edges), on the device:
+ * out[npct][outer central cells] float64, host memory (outer cells in Fortran order of the
+ * outer axes' central parts, slots 2..shape-2).  lo, hi: the percentile axis' limits.
+ * VH_ERR_ARG: not an AggCount, no binners, npct < 1, a percentage that is NaN or outside
+ * [0, 100], out_items != npct * prod(outer shape - 3). */
+int vh_agg_percentile(vh_agg *agg, const double *percentages, int npct, double lo, double hi,
+                      double *out, uint64_t out_items);
 int vh_agg_upload_order(vh_agg *agg, const void *host, uint64_t bytes);   /* (new) combine across ranks */
 int vh_agg_device_ptr(vh_agg *agg, void **grid_dptr, void **grid2_dptr);
 /* Aggregator.reduce(list) superagg.cpp:160-167, 205-212, 252-259, 354-361, 470-480 */

@@ -2,7 +2,8 @@
 
 Restates the parts of ``packages/vaex-core/vaex/dataframe.py`` that drive this hot
 path -- ``count/sum/mean/min/max/std/var/first`` (``:741-1000``), ``minmax``
-(``:1276-1333``), ``limits`` (``:1617+``), ``_binner*``/``_create_binners``
+(``:1276-1333``), ``median_approx`` / ``percentile_approx`` (``:1399-1555``),
+``limits`` (``:1617+``), ``_binner*``/``_create_binners``
 (``:5251-5295``), ``_agg``, ``_set`` (``:474``), ``categorize`` (``:5487-5533``),
 ``groupby``/``binby`` (``:6622-6683``) and the binner specs ``BinnerScalar`` /
 ``BinnerOrdinal`` (``:6737-6800``) -- over columns that are numpy arrays (staged to
@@ -489,6 +490,63 @@ class DataFrame:
             x = np.linspace(vmin, vmax, size + 1)
             out.append(np.interp([f, 1 - f], cumcounts, x))
         return unlistify(waslist, out)
+
+    def median_approx(self, expression, percentage=50., binby=[], limits=None, shape=default_shape,
+                      percentile_shape=256, percentile_limits="minmax", selection=False, delay=False):
+        """dataframe.py:1399-1416: the approximate median (always the 50th percentile, whatever
+        ``percentage`` says, like the reference), possibly on a grid defined by binby."""
+        return self.percentile_approx(expression, 50, binby=binby, limits=limits, shape=shape,
+                                      percentile_shape=percentile_shape, percentile_limits=percentile_limits,
+                                      selection=selection, delay=delay)
+
+    def percentile_approx(self, expression, percentage=50., binby=[], limits=None, shape=default_shape,
+                          percentile_shape=1024, percentile_limits="minmax", selection=False, delay=False):
+        """dataframe.py:1419-1555: the percentile(s) given by ``percentage``, read off the
+        cumulative histogram of the expression over ``percentile_limits`` in ``percentile_shape``
+        bins, possibly per cell of a grid defined by binby.  The count grid
+        (binby + [expression], with edges) stays in HBM and is finished there
+        (``Aggregator.percentile``); only the percentiles are read back.
+
+        A scalar percentage gives the outer (binby) shape, a list of percentages
+        ``(len(percentage),) + outer``, a list of expressions a leading axis over them.  Unlike
+        the reference (which returns a ragged list there), percentages 0 and 100 with binby are
+        broadcast to the outer shape."""
+        from . import hostops
+        from .taskparts import DeviceResult
+        waslist, [expressions] = listify(_ensure_strings(expression))
+        binbys = binby if isinstance(binby, (list, tuple)) else [binby]
+        binbys = [str(b) for b in _ensure_strings(binbys) if b is not None and str(b) != ""]
+        waslist_percentage, [percentages] = listify(percentage)
+        percentages = [float(p) for p in percentages]
+        sel = None if selection in (None, False) else selection
+        percentile_shapes = _expand_shape(percentile_shape, len(expressions))
+        if percentile_limits:
+            percentile_limits = _expand_limits(percentile_limits, len(expressions))
+        else:
+            percentile_limits = (None,) * len(expressions)
+        outer = self._create_binners(binbys, limits, shape, selection=sel)
+        counts, plimits = [], []
+        for expr, pshape, plim in zip(expressions, percentile_shapes, percentile_limits):
+            plim = [float(v) for v in self.limits(expr, plim, selection=sel)]
+            # count(*) over binby + [expression] with edges; keep_device: the part returns the
+            # aggregator (a DeviceResult), its grid still in HBM
+            desc = vagg.count(selection=sel, edges=True)
+            desc.keep_device = True
+            counts.append(desc.add_tasks(self, outer + (self._binner_scalar(expr, plim, pshape),))[1])
+            plimits.append(plim)
+
+        @delayed
+        def finish(*grids):
+            results = []
+            for grid, (lo, hi) in zip(grids, plimits):
+                if isinstance(grid, DeviceResult):
+                    value = grid.agg.percentile(percentages, lo, hi)
+                else:  # keep_device not honoured: the same arithmetic on the host grid
+                    value = hostops.percentile_finish(np.asarray(grid), percentages, lo, hi)
+                results.append(unlistify(waslist_percentage, value))
+            return unlistify(waslist, np.array(results))
+
+        return self._delay(delay, finish(*counts))
 
     def minmax(self, expression, binby=[], limits=None, shape=default_shape, selection=False, delay=False,
                progress=None):

@@ -208,3 +208,41 @@ def occupancy(a):
     firsts = [p[1] for p in parts if p[0]]
     lasts = [p[2] for p in parts if p[0]]
     return nnz, (firsts[0] if firsts else -1), (lasts[-1] if lasts else -1)
+
+
+def percentile_finish(counts, percentages, lo, hi):
+    """The percentile_approx finish (dataframe.py:1461-1529) of a host count grid with edges
+    whose last axis is the percentile axis over [lo, hi]: the arithmetic of the device finish
+    (vh_agg_percentile) in NumPy, for a count grid that did not stay in HBM.  The edge search of
+    grid_find_edges (vaexfast.cpp:1574-1628) as a count: F = #{j : cum[j] < t},
+    left = clip(F - 1, 0, N - 1), right = min(F, N - 1).  Shape (len(percentages),) + the
+    central part of the outer axes; p = 0 / 100 give lo / hi in every cell."""
+    counts = np.asarray(counts)
+    central = counts[(slice(2, -1),) * (counts.ndim - 1) + (slice(1, None),)].astype(np.float64)
+    cum = np.cumsum(central, -1)
+    total = np.sum(central, -1)
+    N = cum.shape[-1]
+    lo, hi = np.float64(lo), np.float64(hi)
+    out = np.empty((len(percentages),) + cum.shape[:-1], np.float64)
+
+    def x(t):
+        F = np.sum(cum < t[..., None], -1)
+        left, right = np.clip(F - 1, 0, N - 1), np.minimum(F, N - 1)
+        cl = np.take_along_axis(cum, left[..., None], -1)[..., 0]
+        cr = np.take_along_axis(cum, right[..., None], -1)[..., 0]
+        u = (t - cl) / (cr - cl)
+        xl = lo + (left - 0.5) * (hi - lo) / np.float64(N - 3)
+        xr = lo + (right - 0.5) * (hi - lo) / np.float64(N - 3)
+        return xl + (xr - xl) * u
+
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for i, p in enumerate(percentages):
+            if p == 0 or p == 100:
+                out[i] = lo if p == 0 else hi
+                continue
+            v = np.array((total + 1) * p / 100.)
+            v[total == 0] = 0
+            f, g = np.floor(v), np.ceil(v)
+            x1, x2 = x(f), x(g)
+            out[i] = x1 + (x2 - x1) * (v - f)
+    return out

@@ -328,6 +328,20 @@ class Aggregator:
         _lib.call("vh_agg_occupancy", self._handle, int(begin), int(end), out)
         return int(out[0]), int(out[1]), int(out[2])
 
+    def percentile(self, percentages, lo, hi):
+        """The percentile_approx finish (dataframe.py:1461-1529) of a count grid whose last
+        binner is the percentile axis over [lo, hi], on the device: an array of shape
+        (len(percentages),) + the central part (slots 2..shape-2) of every other axis."""
+        pcts = np.ascontiguousarray(np.atleast_1d(percentages), dtype=np.float64)
+        outer = tuple(int(s) - 3 for s in self._grid.shapes[:-1])
+        flat = np.empty(len(pcts) * int(np.prod(outer, dtype=np.int64)), dtype=np.float64)
+        self._before_device_use()
+        _lib.call("vh_agg_percentile", self._handle, pcts.ctypes.data, len(pcts), float(lo), float(hi),
+                  flat.ctypes.data, flat.size)
+        # per percentage the cells come back in Fortran order of the outer shape
+        out = flat.reshape((len(pcts),) + outer[::-1])
+        return np.ascontiguousarray(out.transpose((0,) + tuple(range(len(outer), 0, -1))))
+
     def device_order_ptr(self):
         """HBM address of AggFirst's order grid."""
         p, p2 = ctypes.c_void_p(), ctypes.c_void_p()
