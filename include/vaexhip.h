@@ -53,8 +53,16 @@ enum vh_agg_kind {
     VH_AGG_MAX = 3,        /* AggMax_<t>        superagg.cpp:194-239 */
     VH_AGG_FIRST = 4,      /* AggFirst_<t>      superagg.cpp:436-511 */
     VH_AGG_SUM_MOMENT = 5, /* AggSumMoment_<t>  superagg.cpp:391-434 */
-    VH_AGG_NUNIQUE = 6     /* AggNUnique_<t>    agg_hash_primitive.cpp:6-102; create arg: bit 0
+    VH_AGG_NUNIQUE = 6,    /* AggNUnique_<t>    agg_hash_primitive.cpp:6-102; create arg: bit 0
                               dropmissing, bit 1 dropnan */
+    VH_AGG_COV = 7         /* op_cov            vaexfast.cpp:1070-1104 (TaskStatistic OP_COV,
+                              vaex/tasks.py:191-201) over the superagg binners; VH_F64 only;
+                              create arg: the number of value columns N, 1..8, each set with
+                              vh_agg_set_data(index < N).  The grid image (download / upload /
+                              info) is float64 [cell][2N + 2N^2]: N counts, N sums, N x N pair
+                              counts, N x N pair sums (entry r + c * N); uploading takes the
+                              entries r <= c and the column counts for the diagonal counts.
+                              vh_agg_device_ptr gives the 2N + N^2 distinct accumulators. */
 };
 
 /* reductions of the multi-GPU collectives */
@@ -150,7 +158,8 @@ int vh_grid_bin(vh_grid *grid, vh_agg *const *aggs, int naggs, uint64_t length, 
 
 /* ---- Aggregators: superagg.cpp ----------------------------------------- */
 /* Agg<Kind>_<dtype>[_non_native](grid[, moment]) -- `arg` is the moment of
- * AggSumMoment, ignored otherwise.  The grid lives in HBM. */
+ * AggSumMoment, the flags of AggNUnique, the column count of AggCov, ignored otherwise.
+ * The grid lives in HBM. */
 int vh_agg_create(vh_grid *grid, int kind, int dtype, int flip_endian, uint32_t arg, vh_agg **out);
 int vh_agg_destroy(vh_agg *agg);
 /* set_data(buf, index): index 1 = the order column of AggFirst (:449-461) */

@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("VAEX_AMD_LIB", os.path.join(HERE, "libvaexhip.so"))
 DTYPES = ["float64", "float32", "int64", "int32", "int16", "int8",
           "uint64", "uint32", "uint16", "uint8", "bool"]
 DTYPE_CODE = {name: i for i, name in enumerate(DTYPES)}
-AGG_KIND = {"AggCount": 0, "AggSum": 1, "AggMin": 2, "AggMax": 3, "AggFirst": 4, "AggSumMoment": 5, "AggNUnique": 6}
+AGG_KIND = {"AggCount": 0, "AggSum": 1, "AggMin": 2, "AggMax": 3, "AggFirst": 4, "AggSumMoment": 5, "AggNUnique": 6,
+            "AggCov": 7}
 LOC_AUTO, LOC_HOST, LOC_DEVICE = 0, 1, 2
 
 # every symbol the header declares, with (restype, argtypes)

@@ -2,7 +2,8 @@
 
 Same registry (``aggregates``), descriptor classes and argument meaning:
 ``count``, ``sum``, ``mean``, ``min``, ``max``, ``first``, ``std``, ``var``,
-``_sum_moment``.  ``_create_operation`` looks up the HIP-backed class in
+``_sum_moment``, plus ``_cov`` (the fused OP_COV statistic behind ``DataFrame.cov``).
+``_create_operation`` looks up the HIP-backed class in
 :mod:`vaex_amd.superagg` by name + dtype exactly as the reference does
 (``agg.py:111-114``).
 """
@@ -140,6 +141,39 @@ class AggregatorDescriptorNUnique(AggregatorDescriptorBasic):
         return agg_op_type(grid, self.dropmissing, self.dropnan)
 
 
+class AggregatorDescriptorCov(AggregatorDescriptorBasic):
+    """The reference's TaskStatistic(op=OP_COV) (dataframe.py:1242-1248, tasks.py:191-201)
+    as one aggregator over the shared grid."""
+
+    def __init__(self, expressions, selection=None, edges=False):
+        if isinstance(expressions, str) or not isinstance(expressions, (list, tuple)):
+            expressions = [expressions]
+        super().__init__("AggCov", list(expressions), "_cov", multi_args=True, agg_args=[len(expressions)],
+                         selection=selection, edges=edges)
+
+    def _prepare_types(self, df):
+        self.dtype_in = np.dtype("float64")
+        self.dtype_out = np.dtype("float64")
+
+    def add_tasks(self, df, binners):
+        # op_cov multiplies in double whatever the column holds: other dtypes are cast first,
+        # as AggregatorDescriptorVar does
+        exprs = []
+        for e in self.expressions:
+            if df.data_type(e) != np.dtype("float64"):
+                e = str(df[e].astype("float64"))
+            exprs.append(e)
+        self.expressions = exprs
+        self.expression = exprs
+        return super().add_tasks(df, binners)
+
+    def get_result(self, agg_operation):
+        grid = np.asarray(agg_operation)
+        if not self.edges:  # the binner axes only: the trailing axis holds the fields
+            grid = grid[(slice(2, -1),) * (grid.ndim - 1)]
+        return grid
+
+
 class AggregatorDescriptorMulti(AggregatorDescriptor):
     def __init__(self, name, expression, short_name, selection=None, edges=False):
         self.name = name
@@ -256,6 +290,14 @@ def _sum_moment(expression, moment, selection=None, edges=False):
     """Creates a sum of moment aggregator"""
     return AggregatorDescriptorBasic("AggSumMoment", expression, "_sum_moment", agg_args=[moment],
                                      selection=selection, edges=edges)
+
+
+@register
+def _cov(expressions, selection=None, edges=False):
+    """Creates the fused covariance aggregation of N expressions (AggCov): per cell the
+    ``2N + 2N**2`` count / sum / pair count / pair product sum fields of the reference's
+    OP_COV statistic, finished by ``hostops.cov_finish``"""
+    return AggregatorDescriptorCov(expressions, selection=selection, edges=edges)
 
 
 @register

@@ -125,8 +125,6 @@ __global__ __launch_bounds__(256) void k_agg(AggDev a, const uint64_t *idx, uint
 // copy of the grid in the same pass that bins the rows (no indices1d round trip, no global
 // atomic per row -- a few hundred cells hit by every row would serialise on them), then
 // flushes it with one global atomic per touched cell.  Per-row semantics exactly as k_agg.
-constexpr uint64_t LDS_AGG_MAX_BYTES = 96 * 1024;
-
 template <int KIND, typename T> struct LdsCell {
     using G = typename Upcast<T>::type;
     using type = std::conditional_t<KIND == VH_AGG_MIN || KIND == VH_AGG_MAX, T,
@@ -1062,9 +1060,14 @@ template <typename T> T max_fill() {
     }
 }
 
+// items per cell of the HBM grid (AggCov: its distinct accumulators) and of the host image
+// (AggCov: the reference's fields)
+uint64_t grid_items(const vh_agg *a) { return a->kind == VH_AGG_COV ? cov_accs(a->moment) : 1; }
+uint64_t image_items(const vh_agg *a) { return a->kind == VH_AGG_COV ? cov_fields(a->moment) : 1; }
+
 void init_agg_grid(vh_agg *a) {
     const uint64_t L = a->grid->length1d;
-    VH_HIP(hipMemsetAsync(a->g.ptr, 0, L * a->grid_isz, stream()));
+    VH_HIP(hipMemsetAsync(a->g.ptr, 0, L * grid_items(a) * a->grid_isz, stream()));
     if (a->kind == VH_AGG_MIN || a->kind == VH_AGG_MAX) {
         // numeric_limits fill (superagg.cpp:199-204, 246-251)
         const bool mx = a->kind == VH_AGG_MAX;
@@ -1422,8 +1425,13 @@ int vh_grid_info(const vh_grid *g, int *dims, uint64_t *shapes, uint64_t *stride
 
 int vh_agg_create(vh_grid *grid, int kind, int dtype, int flip, uint32_t arg, vh_agg **out) {
     VH_API_BEGIN
-    if (kind < VH_AGG_COUNT || kind > VH_AGG_NUNIQUE) fail(VH_ERR_ARG, "unknown aggregator kind");
+    if (kind < VH_AGG_COUNT || kind > VH_AGG_COV) fail(VH_ERR_ARG, "unknown aggregator kind");
     dtype_itemsize(dtype);
+    if (kind == VH_AGG_COV) {
+        if (arg < 1 || arg > (uint32_t)COV_MAX_N)
+            fail(VH_ERR_ARG, "AggCov takes 1 to " + std::to_string(COV_MAX_N) + " value columns, not " + std::to_string(arg));
+        if (dtype != VH_F64 || flip) fail(VH_ERR_ARG, "AggCov reads native float64 columns only");
+    }
     std::unique_ptr<vh_agg> a(new vh_agg());
     a->grid = grid;
     a->L = grid->length1d;
@@ -1434,11 +1442,12 @@ int vh_agg_create(vh_grid *grid, int kind, int dtype, int flip, uint32_t arg, vh
     switch (kind) {
     case VH_AGG_COUNT: case VH_AGG_NUNIQUE: a->grid_dtype = VH_I64; break;
     case VH_AGG_SUM: case VH_AGG_SUM_MOMENT: a->grid_dtype = upcast_dtype(dtype); break;
+    case VH_AGG_COV: a->grid_dtype = VH_F64; break;
     default: a->grid_dtype = dtype;
     }
     a->grid_isz = dtype_itemsize(a->grid_dtype);
     const uint64_t L = grid->length1d;
-    a->g.ensure(L * a->grid_isz);
+    a->g.ensure(L * grid_items(a.get()) * a->grid_isz);
     if (kind == VH_AGG_FIRST) {
         a->g2.ensure(L * a->grid_isz);
         a->s_key.ensure(L * 8);
@@ -1462,7 +1471,11 @@ int vh_agg_set_data(vh_agg *a, const void *ptr, uint64_t length, int itemsize, i
     if (ndim != 1) fail(VH_ERR_RUNTIME, "Expected a 1d array");
     if (itemsize != dtype_itemsize(a->dtype))
         fail(VH_ERR_RUNTIME, "Itemsize of data and aggregator are not equal");
-    if (a->kind == VH_AGG_FIRST && index == 1) a->data2 = make_col(ptr, length, itemsize, loc);
+    if (a->kind == VH_AGG_COV) {
+        if (index < 0 || index >= (int)a->moment)
+            fail(VH_ERR_ARG, "AggCov column index " + std::to_string(index) + " outside its " + std::to_string(a->moment) + " columns");
+        a->cols[index] = make_col(ptr, length, itemsize, loc);
+    } else if (a->kind == VH_AGG_FIRST && index == 1) a->data2 = make_col(ptr, length, itemsize, loc);
     else a->data = make_col(ptr, length, itemsize, loc);
     VH_API_END
 }
@@ -1493,7 +1506,7 @@ int vh_agg_set_selection_mask(vh_agg *a, const uint8_t *mask, uint64_t length, i
 
 int vh_agg_info(const vh_agg *a, uint64_t *bytes, int *grid_dtype, uint64_t *itemsize) {
     VH_API_BEGIN
-    if (bytes) *bytes = a->grid->length1d * a->grid_isz;
+    if (bytes) *bytes = a->grid->length1d * image_items(a) * a->grid_isz;
     if (grid_dtype) *grid_dtype = a->grid_dtype;
     if (itemsize) *itemsize = a->grid_isz;
     VH_API_END
@@ -1502,6 +1515,10 @@ int vh_agg_info(const vh_agg *a, uint64_t *bytes, int *grid_dtype, uint64_t *ite
 int vh_agg_download(vh_agg *a, void *host, uint64_t bytes) {
     VH_API_BEGIN
     std::lock_guard<std::mutex> lk(a->grid->mu);
+    if (a->kind == VH_AGG_COV) {
+        cov_download(a, host, bytes);
+        return VH_OK;
+    }
     if (bytes != a->grid->length1d * a->grid_isz) fail(VH_ERR_ARG, "download size mismatch");
     nunique_finalize(a);
     if (bytes <= (1u << 20)) {
@@ -1585,6 +1602,10 @@ int vh_agg_upload_order(vh_agg *a, const void *host, uint64_t bytes) {
 int vh_agg_upload(vh_agg *a, const void *host, uint64_t bytes) {
     VH_API_BEGIN
     std::lock_guard<std::mutex> lk(a->grid->mu);
+    if (a->kind == VH_AGG_COV) {
+        cov_upload(a, host, bytes);
+        return VH_OK;
+    }
     if (bytes != a->grid->length1d * a->grid_isz) fail(VH_ERR_ARG, "upload size mismatch");
     if (a->kind == VH_AGG_NUNIQUE) return VH_OK;  // a derived grid (recomputed when read)
     VH_HIP(hipMemcpyAsync(a->g.ptr, host, bytes, hipMemcpyHostToDevice, stream()));
@@ -1608,7 +1629,8 @@ int vh_agg_reduce(vh_agg *a, vh_agg *const *others, int nothers) {
     const uint64_t L = a->grid->length1d;
     for (int k = 0; k < nothers; k++) {
         vh_agg *o = others[k];
-        if (o->kind != a->kind || o->dtype != a->dtype || o->grid->length1d != L)
+        if (o->kind != a->kind || o->dtype != a->dtype || o->grid->length1d != L ||
+            (a->kind == VH_AGG_COV && o->moment != a->moment))
             fail(VH_ERR_RUNTIME, "cannot reduce aggregators of different type or grid");
         if (!L) continue;
         dim3 grd(blocks_for(L, 256)), blk(256);
@@ -1637,6 +1659,12 @@ int vh_agg_reduce(vh_agg *a, vh_agg *const *others, int nothers) {
         case VH_AGG_NUNIQUE:
             nunique_merge(a, o);  // counter::merge (hash_primitives.hpp:393-415)
             break;
+        case VH_AGG_COV: {
+            const uint64_t items = L * cov_accs(a->moment);
+            hipLaunchKernelGGL(k_reduce_add<double>, dim3(blocks_for(items, 256)), blk, 0, stream(), a->g.as<double>(),
+                               o->g.as<double>(), items);
+            break;
+        }
         }
         VH_HIP(hipGetLastError());
     }
@@ -1659,6 +1687,14 @@ int vh_grid_bin(vh_grid *g, vh_agg *const *aggs, int naggs, uint64_t length, int
     for (int k = 0; k < naggs; k++) {
         vh_agg *a = aggs[k];
         if (a->grid != g) fail(VH_ERR_RUNTIME, "aggregator belongs to another grid");
+        if (a->kind == VH_AGG_COV) {
+            for (uint32_t c = 0; c < a->moment; c++) {
+                if (!a->cols[c].set) fail(VH_ERR_RUNTIME, "data" + std::to_string(c) + " not set");
+                check_column(a->cols[c], length, "aggregator data");
+            }
+            if (a->mask.set) check_column(a->mask, length, "aggregator mask");
+            continue;
+        }
         const bool needs_data = a->kind != VH_AGG_COUNT;
         if (needs_data && !a->data.set) fail(VH_ERR_RUNTIME, "data not set");
         if (a->kind == VH_AGG_FIRST && !a->data2.set) fail(VH_ERR_RUNTIME, "data2 not set");
@@ -1726,6 +1762,16 @@ static int scalar_f64_dims(vh_grid *g) {
 }
 
 void run_bin(vh_grid *g, vh_agg *const *aggs, int naggs, uint64_t length) {
+    // AggCov aggregators bin on their own: the others keep the routes they take without them
+    {
+        std::vector<vh_agg *> cov, rest;
+        for (int k = 0; k < naggs; k++) (aggs[k]->kind == VH_AGG_COV ? cov : rest).push_back(aggs[k]);
+        if (!cov.empty() && !rest.empty()) {
+            run_bin(g, rest.data(), (int)rest.size(), length);
+            run_bin(g, cov.data(), (int)cov.size(), length);
+            return;
+        }
+    }
     bool all_fusable = naggs <= MAX_FUSED_AGGS;
     for (int k = 0; k < naggs && all_fusable; k++) all_fusable = fusable(aggs[k]);
     bool any_host = false;
@@ -1738,6 +1784,7 @@ void run_bin(vh_grid *g, vh_agg *const *aggs, int naggs, uint64_t length) {
         note(aggs[k]->data);
         note(aggs[k]->data2);
         note(aggs[k]->mask);
+        for (const ColumnRef &c : aggs[k]->cols) note(c);
     }
     const uint64_t L = g->length1d;
     // count / sum of other native dtypes without masks on grids beyond the LDS sub-grid size
@@ -1789,6 +1836,7 @@ void run_bin(vh_grid *g, vh_agg *const *aggs, int naggs, uint64_t length) {
             pipe.add(aggs[k]->data);
             pipe.add(aggs[k]->data2);
             pipe.add(aggs[k]->mask);
+            for (const ColumnRef &c : aggs[k]->cols) pipe.add(c);
         }
         pipe.plan(std::min(chunk_max, std::max<uint64_t>(length, 1)));
         if (length) pipe.issue(0, 0, std::min(chunk_max, length));
@@ -1871,7 +1919,9 @@ void run_bin(vh_grid *g, vh_agg *const *aggs, int naggs, uint64_t length) {
             for (int k = 0; k < naggs; k++) ads.push_back(agg_dev(aggs[k], st));
             // small grids: LDS sub-grid per workgroup for every kind but AggFirst / AggNUnique
             const bool small = L * 8 <= LDS_AGG_MAX_BYTES;
-            auto lds_ok = [&](int kind) { return small && kind != VH_AGG_FIRST && kind != VH_AGG_NUNIQUE; };
+            auto lds_ok = [&](int kind) {
+                return small && kind != VH_AGG_FIRST && kind != VH_AGG_NUNIQUE && kind != VH_AGG_COV;
+            };
             // AggFirst over a large grid: the tile-partitioned engine (first.hip) fills its
             // s_key / s_row scratch without per-row global atomics; k_first_c merges as below
             for (int k = 0; k < naggs; k++) {
@@ -1946,6 +1996,8 @@ void run_bin(vh_grid *g, vh_agg *const *aggs, int naggs, uint64_t length) {
             }
             for (int k = 0; k < naggs && !idx; k++) {
                 if (tdone[k] || lds_ok(ads[k].kind) || (first_lds && ads[k].kind == VH_AGG_FIRST)) continue;
+                // AggCov reads the u16 cells on a grid its LDS kernel takes, and nothing on a 0-d grid
+                if (ads[k].kind == VH_AGG_COV && (plan.nb == 0 || (cells_ok && cov_fits_lds(L, aggs[k]->moment)))) continue;
                 g->ws.idx.ensure(len * 8);
                 idx = g->ws.idx.as<uint64_t>();
                 compute_idx(plan, len, idx);
@@ -2063,6 +2115,17 @@ void run_bin(vh_grid *g, vh_agg *const *aggs, int naggs, uint64_t length) {
             for (int k = 0; k < naggs; k++) {
                 AggDev &ad = ads[k];
                 if (done[k]) continue;
+                if (ad.kind == VH_AGG_COV) {
+                    CovDev cd{};
+                    cd.n = (int32_t)aggs[k]->moment;
+                    for (int c = 0; c < cd.n; c++) cd.col[c] = reinterpret_cast<const double *>(st.get(aggs[k]->cols[c]));
+                    cd.mask = ad.mask;
+                    cd.grid = reinterpret_cast<double *>(ad.grid);
+                    const bool by_cells = plan.nb > 0 && cells_ok && cov_fits_lds(L, cd.n);
+                    if (by_cells) make_cells();
+                    cov_bin(cd, by_cells ? cells : nullptr, plan.nb > 0 && !by_cells ? idx : nullptr, len, L);
+                    continue;
+                }
                 if (lds_ok(ad.kind) && cells_ok) {
                     make_cells();
                     TimedScope ts("bin_aggregate_lds");

@@ -414,6 +414,9 @@ int vh_comm_agg_allreduce(vh_comm *c, vh_agg *a) {
     case VH_AGG_MIN: case VH_AGG_MAX:
         comm_allreduce_dev(c, a->g.ptr, L, a->dtype, a->kind == VH_AGG_MIN ? VH_OP_MIN : VH_OP_MAX);
         break;
+    case VH_AGG_COV:  // the distinct accumulators, all float64 sums
+        comm_allreduce_dev(c, a->g.ptr, L * cov_accs(a->moment), VH_F64, VH_OP_SUM);
+        break;
     case VH_AGG_FIRST: {
         const int isz = dtype_itemsize(a->dtype);
         const uint64_t b = (uint64_t)isz * L;

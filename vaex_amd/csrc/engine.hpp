@@ -16,6 +16,9 @@ namespace vh {
 constexpr int MAX_DIM = 16;          // agg.hpp:25
 constexpr int MAX_FUSED_AGGS = 4;
 constexpr uint64_t LDS_FUSED_MAX = 64 * 1024;  // per-workgroup privatised grid budget
+// small grids of the generic path: a workgroup's LDS copy of one aggregator's grid
+constexpr uint64_t LDS_AGG_MAX_BYTES = 96 * 1024;
+constexpr int COV_MAX_N = 8;  // value columns of an AggCov
 
 // one column as handed over by set_data / set_data_mask
 struct ColumnRef {
@@ -222,12 +225,14 @@ struct vh_grid {
 struct vh_agg {
     vh_grid *grid = nullptr;
     int kind = 0, dtype = VH_F64, flip = 0;
-    uint32_t moment = 0;   // AggSumMoment moment; AggNUnique: bit 0 dropmissing, bit 1 dropnan
+    uint32_t moment = 0;   // AggSumMoment moment; AggNUnique: bit 0 dropmissing, bit 1 dropnan;
+                           // AggCov: the number of value columns N
     int grid_dtype = VH_I64;
     int grid_isz = 8;
     vh::DevBuf g, g2;          // grid, AggFirst order grid / AggNUnique per-cell null counts
     vh::DevBuf s_key, s_row;   // AggFirst per-chunk scratch / AggNUnique per-cell nan counts
     vh::ColumnRef data, data2, mask;
+    vh::ColumnRef cols[vh::COV_MAX_N];  // AggCov value columns (set_data index < moment)
     // AggNUnique (agg_hash_primitive.cpp:6-102): the (cell, value) pairs seen so far, kept
     // as an unordered list, deduplicated by sort when the grid is read or the list grows
     bool has_selection = false;
@@ -243,4 +248,23 @@ void nunique_init(vh_agg *a);
 void nunique_collect(vh_agg *a, const AggDev &ad, const uint64_t *idx, uint64_t len);
 void nunique_merge(vh_agg *a, vh_agg *o);
 void nunique_finalize(vh_agg *a);
+
+// AggCov (cov.hip): op_cov (vaexfast.cpp:1070-1104) over the superagg binners.  The HBM grid
+// holds per cell the 2N + N^2 distinct accumulators, all float64, contiguous:
+//   [0, N) counts, [N, 2N) sums, then the pair counts of r < c at c(c-1)/2 + r, then the pair
+//   sums of r <= c at c(c+1)/2 + r
+// and is expanded to the reference's 2N + 2N^2 fields when it is read.
+struct CovDev {
+    int32_t n, pad;
+    const double *col[COV_MAX_N];
+    const uint8_t *mask;  // 1 = keep
+    double *grid;
+};
+constexpr uint64_t cov_accs(uint64_t n) { return 2 * n + n * n; }
+constexpr uint64_t cov_fields(uint64_t n) { return 2 * n + 2 * n * n; }
+inline bool cov_fits_lds(uint64_t L, uint64_t n) { return L * cov_accs(n) * 8 <= LDS_AGG_MAX_BYTES; }
+// rows [0, len) of a chunk: the row's cell from `cells` (u16), else `idx`, else cell 0 (L == 1)
+void cov_bin(const CovDev &cd, const uint16_t *cells, const uint64_t *idx, uint64_t len, uint64_t L);
+void cov_download(vh_agg *a, void *host, uint64_t bytes);      // expanded fields, [L][F]
+void cov_upload(vh_agg *a, const void *host, uint64_t bytes);  // from expanded fields
 }  // namespace vh

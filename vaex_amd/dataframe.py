@@ -3,7 +3,7 @@
 Restates the parts of ``packages/vaex-core/vaex/dataframe.py`` that drive this hot
 path -- ``count/sum/mean/min/max/std/var/first`` (``:741-1000``), ``minmax``
 (``:1276-1333``), ``median_approx`` / ``percentile_approx`` (``:1399-1555``),
-``limits`` (``:1617+``), ``_binner*``/``_create_binners``
+``cov`` / ``covar`` / ``correlation`` (``:1067-1272``), ``limits`` (``:1617+``), ``_binner*``/``_create_binners``
 (``:5251-5295``), ``_agg``, ``_set`` (``:474``), ``categorize`` (``:5487-5533``),
 ``groupby``/``binby`` (``:6622-6683``) and the binner specs ``BinnerScalar`` /
 ``BinnerOrdinal`` (``:6737-6800``) -- over columns that are numpy arrays (staged to
@@ -39,6 +39,10 @@ def _ensure_strings(es):
     if isinstance(es, (list, tuple)):
         return [_ensure_string(e) for e in es]
     return _ensure_string(es)
+
+
+def _issequence(x):
+    return isinstance(x, (tuple, list, np.ndarray))
 
 
 class BinnerScalar:
@@ -652,6 +656,88 @@ class DataFrame:
             progress=None, edges=False, array_type=None):
         return self._compute_agg("var", expression, binby, limits, shape, selection, delay, edges, progress,
                                  array_type=array_type)
+
+    def _cov_values(self, pairs, binby, limits, shape, selection):
+        """One AggCov per expression list in ``pairs`` on the shared binby grid: the delayed
+        covariance matrices ``outer + (N, N)`` (one pass over the columns for all of them)."""
+        from . import hostops
+        sel = None if selection is False else selection
+        binners = self._create_binners(binby, limits, shape, selection=sel)
+        results = []
+        for expressions in pairs:
+            N = len(expressions)
+            _, values = vagg._cov(list(expressions), selection=sel).add_tasks(self, binners)
+            results.append(delayed(lambda v, N=N: hostops.cov_finish(np.asarray(v), N))(values))
+        return results
+
+    def cov(self, x, y=None, binby=[], limits=None, shape=default_shape, selection=False, delay=False, progress=None):
+        """dataframe.py:1192-1272: the covariance matrix of x and y, or of the expressions in the
+        sequence x, possibly per cell of a grid defined by binby: shape ``outer + (N, N)``.
+        One fused pass (AggCov) over the N columns and the binby columns; the cell of a row
+        comes from the binners every other method here uses."""
+        selection = _ensure_strings(selection)
+        if y is None:
+            if not isinstance(x, (list, tuple, np.ndarray)):
+                raise ValueError("if y argument is not given, x is expected to be sequence, not %r" % (x,))
+            expressions = list(x)
+        else:
+            expressions = [x, y]
+        expressions = _ensure_strings(expressions)
+        [value] = self._cov_values([expressions], binby, limits, shape, selection)
+        return self._delay(delay, value)
+
+    def covar(self, x, y, binby=[], limits=None, shape=default_shape, selection=False, delay=False, progress=None):
+        """dataframe.py:1067-1118: the covariance cov[x, y] = mean(x * y) - mean(x) * mean(y),
+        possibly on a grid defined by binby; lists in x and y give a leading axis.  It is
+        element ``[..., 0, 1]`` of :meth:`cov`'s fused pass: the means over the non-NaN values of
+        each column, mean(x * y) over the rows where both are non-NaN; no product column is
+        formed.  Unlike the reference, whose count of the product column drops a row where
+        ``x * y`` is NaN although neither factor is (``inf * 0``), that row stays in the pair
+        count here."""
+        waslist, [xlist, ylist] = listify(_ensure_strings(x), _ensure_strings(y))
+        selection = _ensure_strings(selection)
+        covs = self._cov_values(list(zip(xlist, ylist)), binby, limits, shape, selection)
+
+        @delayed
+        def finish(*covs):
+            return np.array(unlistify(waslist, [c[..., 0, 1] for c in covs]))
+
+        return self._delay(delay, finish(*covs))
+
+    def correlation(self, x, y=None, binby=[], limits=None, shape=default_shape, sort=False, sort_key=np.abs,
+                    selection=False, delay=False, progress=None):
+        """dataframe.py:1121-1189: the correlation coefficient cov[x, y] / (std[x] * std[y]),
+        possibly on a grid defined by binby.  With y None, x is a pair or a list of pairs; with
+        ``sort`` the result is ``(correlations[indices], sorted_x)``, ordered by descending
+        ``sort_key``.  Each pair is one AggCov (N = 2) on the shared grid."""
+        if y is None:
+            if not isinstance(x, (tuple, list)):
+                raise ValueError("if y not given, x is expected to be a list or tuple, not %r" % x)
+            if _issequence(x) and not _issequence(x[0]) and len(x) == 2:
+                x = [x]
+            if not (_issequence(x) and all([_issequence(k) and len(k) == 2 for k in x])):
+                raise ValueError("if y not given, x is expected to be a list of lists with length 2, not %r" % x)
+            waslist = True
+            xlist, ylist = zip(*x)
+        else:
+            waslist, [xlist, ylist] = listify(x, y)
+        xlist = _ensure_strings(list(xlist))
+        ylist = _ensure_strings(list(ylist))
+        selection = _ensure_strings(selection)
+        covs = self._cov_values(list(zip(xlist, ylist)), binby, limits, shape, selection)
+
+        @delayed
+        def finish(*covs):
+            with np.errstate(divide="ignore", invalid="ignore"):  # nan for an empty cell is fine
+                correlations = [c[..., 0, 1] / (c[..., 0, 0] * c[..., 1, 1]) ** 0.5 for c in covs]
+            if sort:
+                correlations = np.array(correlations)
+                indices = np.argsort(sort_key(correlations) if sort_key else correlations)[::-1]
+                sorted_x = list([x[k] for k in indices])
+                return correlations[indices], sorted_x
+            return np.array(unlistify(waslist, correlations))
+
+        return self._delay(delay, finish(*covs))
 
     def first(self, expression, order_expression, binby=[], limits=None, shape=default_shape, selection=False,
               delay=False, edges=False, progress=None, array_type=None):

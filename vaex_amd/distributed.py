@@ -39,7 +39,7 @@ def _comm(comm):
 
 def _reduce_op_for(kind):
     return {"AggCount": "sum", "AggSum": "sum", "AggSumMoment": "sum", "AggMin": "min", "AggMax": "max",
-            "AggFirst": "first"}[kind]
+            "AggFirst": "first", "AggCov": "sum"}[kind]
 
 
 def combine_grids(kind, grid, order=None, comm=None):
@@ -69,7 +69,8 @@ def allreduce_aggs(aggs, comm=None):
         if comm.device:
             comm.agg_allreduce(agg)
         else:
-            grid = np.empty(agg.grid.length1d, agg._grid_dtype)
+            # the host image (AggCov: its fields per cell)
+            grid = np.empty(agg._nbytes // agg._grid_dtype.itemsize, agg._grid_dtype)
             _lib.call("vh_agg_download", agg._handle, grid.ctypes.data, agg._nbytes)
             order = None
             if agg._kind == "AggFirst":

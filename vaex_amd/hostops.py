@@ -246,3 +246,24 @@ def percentile_finish(counts, percentages, lo, hi):
             x1, x2 = x(f), x(g)
             out[i] = x1 + (x2 - x1) * (v - f)
     return out
+
+
+def cov_finish(values, N):
+    """The finish of DataFrame.cov (dataframe.py:1251-1268) over an AggCov grid: ``values``
+    has ``2N + 2N**2`` fields on its last axis, the result the shape ``outer + (N, N)``."""
+    values = np.asarray(values)
+    counts = values[..., :N]
+    sums = values[..., N:2 * N]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        means = sums / counts
+    # matrix of means * means.T
+    meansxy = means[..., None] * means[..., None, :]
+    counts = values[..., 2 * N:2 * N + N ** 2]
+    sums = values[..., 2 * N + N ** 2:]
+    shape = counts.shape[:-1] + (N, N)
+    counts = counts.reshape(shape)
+    sums = sums.reshape(shape)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        moments2 = sums / counts
+    with np.errstate(invalid="ignore"):  # inf - inf in a cell holding an infinite value
+        return moments2 - meansxy

@@ -9,7 +9,7 @@ reference's pybind11 module (``packages/vaex-core/src/superagg.cpp:586-626``,
 * ``BinnerScalar_<dtype>[_non_native](expression, vmin, vmax, bins)``
 * ``BinnerOrdinal_<dtype>[_non_native](expression, ordinal_count, min_value)``
 * ``Agg{Count,Sum,Min,Max,First}_<dtype>[_non_native](grid)``,
-  ``AggSumMoment_<dtype>[_non_native](grid, moment)`` with ``set_data(ar, index)``,
+  ``AggSumMoment_<dtype>[_non_native](grid, moment)``, ``AggCov_float64(grid, N)`` with ``set_data(ar, index)``,
   ``set_data_mask``, ``clear_data_mask``, ``reduce``, ``__sizeof__``, ``.grid``
   and a live, writable, Fortran-ordered array view (``np.asarray(agg)``).
 
@@ -395,8 +395,53 @@ class _AggNUniqueBase(Aggregator):
         pass  # the grid is derived from the pairs: writes through a view do not feed back
 
 
+class _AggCovBase(Aggregator):
+    """AggCov_float64(grid, N): the reference's OP_COV statistic (op_cov,
+    vaexfast.cpp:1070-1104; TaskStatistic, tasks.py:191-201) over this module's binners.  N
+    float64 columns (``set_data(ar, index)``, index < N, 1 <= N <= 8); per grid cell
+    ``2N + 2N**2`` float64 fields: N counts of non-NaN values, N sums, N x N counts of rows
+    where both columns are non-NaN, N x N sums of their products (entry ``r + c * N``).  The
+    array view has shape ``grid.shapes + (fields,)``, the fields contiguous within a cell."""
+
+    _kind = "AggCov"
+
+    def __init__(self, grid, N):
+        super().__init__(grid, N)
+        self.N = int(N)
+        self.fields = 2 * self.N + 2 * self.N ** 2
+
+    def set_data(self, ar, index=0):
+        ptr, length, itemsize, ndim, loc, keep = _column(ar)
+        _lib.call("vh_agg_set_data", self._handle, ptr, length, itemsize, ndim, int(index), loc)
+        self._refs[("data", int(index))] = keep
+
+    def _ensure_host(self):
+        if self._host is None:
+            self._host = _lib.pinned_empty(self._grid.length1d * self.fields, self._grid_dtype)
+            self._device_newer = True
+        super()._ensure_host()
+
+    @property
+    def __array_interface__(self):
+        """Live writable view, shape = binner shapes + (fields,): Fortran strides over the
+        binner axes, the field axis fastest.  Written pair entries are read back from the
+        half ``r <= c`` and the diagonal pair counts from the column counts."""
+        self._ensure_host()
+        self._exposed = True
+        g = self._grid
+        step = 8 * self.fields
+        return {
+            "shape": tuple(g.shapes) + (self.fields,),
+            "typestr": self._grid_dtype.str,
+            "data": (self._host.ctypes.data, False),
+            "strides": tuple(s * step for s in g.strides) + (8,),
+            "version": 3,
+        }
+
+
 def _register():
     ns = globals()
+    ns["AggCov_float64"] = type("AggCov_float64", (_AggCovBase,), {"_dtype": "float64", "_flip": 0, "__module__": __name__})
     for dtype in DTYPES:
         for flip in (0, 1):
             postfix = dtype + ("_non_native" if flip else "")
