@@ -194,6 +194,16 @@ int vh_agg_occupancy(vh_agg *agg, uint64_t begin, uint64_t end, int64_t *out3);
  * [0, 100], out_items != npct * prod(outer shape - 3). */
 int vh_agg_percentile(vh_agg *agg, const double *percentages, int npct, double lo, double hi,
                       double *out, uint64_t out_items);
+/* mutual information finish of an AggCount grid whose binners 0 and 1 are the x and y axes and
+ * whose binners 2.. are the outer (binby) axes (dataframe.py:622-718 calculate +
+ * kld.py:13-21 + utils.py:119-142), on the device: out[outer central cells] float64, host
+ * memory (Fortran order of the outer axes' central parts, as vh_agg_percentile).  Per cell over
+ * the central Mx x My part of its x-y slab (every edge slot of every axis ignored):
+ * sum over a > 0 of p * log(p / q), p = a / T, q = rx * cy / (T * T); an empty cell gives 0.
+ * The float64 sum has a fixed order per shape: two calls on one grid agree bit for bit.
+ * VH_ERR_ARG: not an AggCount with an int64 grid, fewer than 2 or more than 16 binners, an x or
+ * y axis of shape < 4, out_items != prod(outer shape - 3), out null with cells to write. */
+int vh_agg_mutual_information(vh_agg *agg, double *out, uint64_t out_items);
 int vh_agg_upload_order(vh_agg *agg, const void *host, uint64_t bytes);   /* (new) combine across ranks */
 int vh_agg_device_ptr(vh_agg *agg, void **grid_dptr, void **grid2_dptr);
 /* Aggregator.reduce(list) superagg.cpp:160-167, 205-212, 252-259, 354-361, 470-480 */

@@ -77,6 +77,7 @@ SIGNATURES = {
     "vh_agg_download_order": (_i32, [_vp, _vp, _u64]),
     "vh_agg_occupancy": (_i32, [_vp, _u64, _u64, _vp]),
     "vh_agg_percentile": (_i32, [_vp, _vp, _i32, _dbl, _dbl, _vp, _u64]),
+    "vh_agg_mutual_information": (_i32, [_vp, _vp, _u64]),
     "vh_agg_upload_order": (_i32, [_vp, _vp, _u64]),
     "vh_agg_device_ptr": (_i32, [_vp, _p(_vp), _p(_vp)]),
     "vh_agg_reduce": (_i32, [_vp, _p(_vp), _i32]),

@@ -3,7 +3,8 @@
 Restates the parts of ``packages/vaex-core/vaex/dataframe.py`` that drive this hot
 path -- ``count/sum/mean/min/max/std/var/first`` (``:741-1000``), ``minmax``
 (``:1276-1333``), ``median_approx`` / ``percentile_approx`` (``:1399-1555``),
-``cov`` / ``covar`` / ``correlation`` (``:1067-1272``), ``limits`` (``:1617+``), ``_binner*``/``_create_binners``
+``cov`` / ``covar`` / ``correlation`` (``:1067-1272``), ``mutual_information``
+(``:622-718``), ``limits`` (``:1617+``), ``_binner*``/``_create_binners``
 (``:5251-5295``), ``_agg``, ``_set`` (``:474``), ``categorize`` (``:5487-5533``),
 ``groupby``/``binby`` (``:6622-6683``) and the binner specs ``BinnerScalar`` /
 ``BinnerOrdinal`` (``:6737-6800``) -- over columns that are numpy arrays (staged to
@@ -549,6 +550,86 @@ class DataFrame:
                     value = hostops.percentile_finish(np.asarray(grid), percentages, lo, hi)
                 results.append(unlistify(waslist_percentage, value))
             return unlistify(waslist, np.array(results))
+
+        return self._delay(delay, finish(*counts))
+
+    def mutual_information(self, x, y=None, mi_limits=None, mi_shape=256, binby=[], limits=None, shape=default_shape,
+                           sort=False, selection=False, delay=False):
+        """dataframe.py:622-718: the mutual information between x and y, estimated on a grid of
+        ``mi_shape`` bins over ``mi_limits``, possibly per cell of a grid defined by binby.  The
+        count grid ([x, y] + binby, with edges) stays in HBM and is finished there
+        (``Aggregator.mutual_information``); one float64 per binby cell is read back.
+
+        ``x`` with ``y`` is one pair (a 0-d result, or the binby shape); two equally long lists, or
+        a list of pairs in ``x`` alone, give a leading axis over the pairs.  ``mi_limits``:
+        ``[[xlo, xhi], [ylo, yhi]]`` (or ``"minmax"``, the default) for every pair, or a list of
+        those, one per pair.  ``sort=True`` returns the values in descending order and the pairs
+        in that order; combined with binby it raises ValueError (the reference's argsort over
+        the per-cell values does not order pairs).  Unlike the reference, binby is not limited
+        to 3 axes.  The limits of an expression are resolved once per call, however many pairs
+        it occurs in."""
+        from . import hostops
+        from .taskparts import DeviceResult
+        if y is None:
+            waslist, [pairs] = listify(x)
+        else:
+            waslist, [xs, ys] = listify(x, y)
+            if len(xs) != len(ys):
+                raise ValueError("x and y hold %d and %d expressions" % (len(xs), len(ys)))
+            pairs = list(zip(xs, ys))
+        for pair in pairs:
+            if not _issequence(pair) or len(pair) != 2:
+                raise ValueError("mutual_information wants pairs of expressions, not %r" % (pair,))
+        pairs = [_ensure_strings(list(pair)) for pair in pairs]
+
+        def one_pair_limits(value):  # [xlim, ylim], each None, a string or [lo, hi]
+            return _issequence(value) and len(value) == 2 and all(
+                v is None or isinstance(v, str) or (_issequence(v) and len(v) == 2 and not _issequence(v[0]))
+                for v in value)
+
+        if mi_limits is None or isinstance(mi_limits, str) or one_pair_limits(mi_limits):
+            pair_limits = [_expand_limits(mi_limits, 2)] * len(pairs)
+        else:
+            if len(mi_limits) != len(pairs):
+                raise ValueError("mi_limits holds %d entries for %d pairs" % (len(mi_limits), len(pairs)))
+            pair_limits = [_expand_limits(lim, 2) for lim in mi_limits]
+        mi_shapes = _expand_shape(mi_shape, 2)
+        binbys = binby if isinstance(binby, (list, tuple)) else [binby]
+        binbys = [str(b) for b in _ensure_strings(binbys) if b is not None and str(b) != ""]
+        if sort and binbys:
+            raise ValueError("sort=True orders scalar values: it cannot be combined with binby")
+        sel = None if selection in (None, False) else selection
+        outer = self._create_binners(binbys, limits, shape, selection=sel)
+        resolved = {}  # (expression, limit) -> [lo, hi]: one min/max pass per distinct one
+
+        def axis_limits(e, lim):
+            key = (e, lim if lim is None or isinstance(lim, str) else tuple(float(v) for v in lim))
+            if key not in resolved:
+                resolved[key] = [float(v) for v in self.limits(e, lim, selection=sel)]
+            return resolved[key]
+
+        counts = []
+        for pair, plims in zip(pairs, pair_limits):
+            axes = tuple(self._binner_scalar(e, axis_limits(e, lim), s) for e, lim, s in zip(pair, plims, mi_shapes))
+            # count(*) over [x, y] + binby with edges; keep_device: the part returns the
+            # aggregator (a DeviceResult), its grid still in HBM
+            desc = vagg.count(selection=sel, edges=True)
+            desc.keep_device = True
+            counts.append(desc.add_tasks(self, axes + outer)[1])
+
+        @delayed
+        def finish(*grids):
+            values = []
+            for grid in grids:
+                if isinstance(grid, DeviceResult):
+                    values.append(grid.agg.mutual_information())
+                else:  # keep_device not honoured: the same arithmetic on the host grid
+                    values.append(hostops.mutual_information_finish(np.asarray(grid)))
+            if sort:
+                mi_list = np.array(values)
+                indices = np.argsort(mi_list)[::-1]
+                return mi_list[indices], [pairs[k] for k in indices]
+            return np.array(unlistify(waslist, values))
 
         return self._delay(delay, finish(*counts))
 

@@ -248,6 +248,25 @@ def percentile_finish(counts, percentages, lo, hi):
     return out
 
 
+def mutual_information_finish(counts):
+    """The mutual_information finish (dataframe.py:663-688 + kld.py:13-21) of a host count grid
+    with edges whose first two axes are x and y: the arithmetic of the device finish
+    (vh_agg_mutual_information) in NumPy, for a count grid that did not stay in HBM.  Over the
+    central part of every axis, per outer cell: the sum over a > 0 of p * log(p / q) with
+    p = a / T and q = rx * cy / (T * T) (T * T: the closed form of the reference's Q.sum()); an
+    empty cell gives 0.  Shape: the central part of the outer axes."""
+    counts = np.asarray(counts)
+    a = counts[(slice(2, -1),) * counts.ndim]
+    T = a.sum(axis=(0, 1), dtype=np.int64).astype(np.float64)
+    rx = a.sum(axis=1, dtype=np.int64, keepdims=True).astype(np.float64)
+    cy = a.sum(axis=0, dtype=np.int64, keepdims=True).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = a.astype(np.float64) / T
+        q = (rx * cy) / (T * T)
+        terms = np.where(a > 0, p * np.log(p / q), 0.0)
+    return np.asarray(terms.sum(axis=(0, 1)))
+
+
 def cov_finish(values, N):
     """The finish of DataFrame.cov (dataframe.py:1251-1268) over an AggCov grid: ``values``
     has ``2N + 2N**2`` fields on its last axis, the result the shape ``outer + (N, N)``."""

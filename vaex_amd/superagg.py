@@ -342,6 +342,18 @@ class Aggregator:
         out = flat.reshape((len(pcts),) + outer[::-1])
         return np.ascontiguousarray(out.transpose((0,) + tuple(range(len(outer), 0, -1))))
 
+    def mutual_information(self):
+        """The mutual_information finish (dataframe.py:663-688 + kld.py:13-21) of a count grid
+        whose binners 0 and 1 are the x and y axes, on the device: one float64 per cell of the
+        central part (slots 2..shape-2) of the other axes, indexed [binby0, binby1, ...]; a 0-d
+        array without them.  Every edge slot of every axis is ignored."""
+        outer = tuple(max(int(s) - 3, 0) for s in self._grid.shapes[2:])
+        flat = np.empty(int(np.prod(outer, dtype=np.int64)), dtype=np.float64)
+        self._before_device_use()
+        _lib.call("vh_agg_mutual_information", self._handle, flat.ctypes.data, flat.size)
+        # the cells come back in Fortran order of the outer shape
+        return flat.reshape(outer[::-1]).transpose().copy()
+
     def device_order_ptr(self):
         """HBM address of AggFirst's order grid."""
         p, p2 = ctypes.c_void_p(), ctypes.c_void_p()
