@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 namespace vh {
 
@@ -26,8 +27,10 @@ constexpr int EX_THREADS = 256;
 // opcodes (vaex_amd/expr.py mirrors these numbers)
 enum : uint32_t {
     OP_COL = 0, OP_CONST = 1, OP_I2F = 2, OP_F2I = 3, OP_ROUND_F32 = 4, OP_WRAP = 5, OP_U2F = 6,
+    OP_I2F32 = 7, OP_U2F32 = 8, OP_F2U = 9,
     OP_ADD_F = 10, OP_SUB_F = 11, OP_MUL_F = 12, OP_DIV_F = 13, OP_FLOORDIV_F = 14, OP_MOD_F = 15,
     OP_POW_F = 16, OP_NEG_F = 17, OP_ABS_F = 18, OP_MIN_F = 19, OP_MAX_F = 20, OP_ARCTAN2 = 21,
+    OP_FLOORDIV_F32 = 22, OP_MOD_F32 = 23,
     OP_ADD_I = 30, OP_SUB_I = 31, OP_MUL_I = 32, OP_FLOORDIV_I = 33, OP_MOD_I = 34, OP_NEG_I = 35,
     OP_ABS_I = 36, OP_AND_I = 37, OP_OR_I = 38, OP_XOR_I = 39, OP_INV_I = 40, OP_MIN_I = 41, OP_MAX_I = 42,
     OP_SHL_I = 43, OP_SHR_I = 44, OP_POW_I = 45,
@@ -40,6 +43,7 @@ enum : uint32_t {
     OP_FLOOR = 93, OP_CEIL = 94, OP_ISNAN = 95, OP_ISFINITE = 96, OP_ISINF = 97, OP_LOG1P = 98,
     OP_EXPM1 = 99, OP_LOG2 = 100, OP_EXP2 = 101, OP_TRUNC = 102, OP_RINT = 103,
     OP_WHERE = 110,
+    OP_FLOORDIV_U = 120, OP_MOD_U = 121, OP_MIN_U = 122, OP_MAX_U = 123, OP_SHR_U = 124, OP_POW_U = 125,
 };
 
 struct ExprProg {
@@ -87,45 +91,50 @@ __device__ inline int64_t mod_i(int64_t a, int64_t b) {
 }
 
 // numpy's float floor_divide / remainder (npy_divmod): the remainder takes the divisor's
-// sign, the quotient is floored and corrected by one where fmod rounds
-__device__ inline void divmod_f(double a, double b, double *q, double *r) {
-    double mod = fmod(a, b);
-    if (b == 0.0) {
+// sign, the quotient is floored and corrected by one where fmod rounds.  T = float for float32
+// nodes: numpy runs the same steps in float32, and a quotient beyond 2^24 taken in float64 and
+// rounded afterwards can land on another float32 than (a - mod) / b rounded first, floored then
+template <typename T> __device__ inline void divmod_f(T a, T b, T *q, T *r) {
+    T mod = fmod(a, b);
+    if (b == (T)0.0) {
         *r = mod;
         *q = a / b;
         return;
     }
-    double div = (a - mod) / b;
-    if (mod != 0.0) {
+    T div = (a - mod) / b;
+    if (mod != (T)0.0) {
         if ((b < 0) != (mod < 0)) {
             mod += b;
-            div -= 1.0;
+            div -= (T)1.0;
         }
     } else {
-        mod = copysign(0.0, b);
+        mod = copysign((T)0.0, b);
     }
-    double fl;
-    if (div != 0.0) {
+    T fl;
+    if (div != (T)0.0) {
         fl = floor(div);
-        if (div - fl > 0.5) fl += 1.0;
+        if (div - fl > (T)0.5) fl += (T)1.0;
     } else {
-        fl = copysign(0.0, a / b);
+        fl = copysign((T)0.0, a / b);
     }
     *q = fl;
     *r = mod;
 }
 
-__device__ inline int64_t pow_i(int64_t base, int64_t e) {
-    if (e < 0) return 0;  // numpy raises for integer ** negative; the host rejects constants
-    int64_t r = 1;
-    uint64_t ub = (uint64_t)base, ur = 1;
+// base ** e modulo 2^64 (the node's WRAP narrows it): the same bits for signed and unsigned
+__device__ inline uint64_t pow_u(uint64_t ub, uint64_t e) {
+    uint64_t ur = 1;
     while (e) {
         if (e & 1) ur *= ub;
         ub *= ub;
         e >>= 1;
     }
-    r = (int64_t)ur;
-    return r;
+    return ur;
+}
+
+__device__ inline int64_t pow_i(int64_t base, int64_t e) {
+    if (e < 0) return 0;  // numpy raises for integer ** negative; the host rejects constants
+    return (int64_t)pow_u((uint64_t)base, (uint64_t)e);
 }
 
 template <bool MATH> __device__ inline uint64_t unary(uint32_t op, uint32_t arg, uint64_t x) {
@@ -139,8 +148,9 @@ template <bool MATH> __device__ inline uint64_t unary(uint32_t op, uint32_t arg,
         case OP_LOG10: return fb(log10(f));
         case OP_LOG2: return fb(log2(f));
         case OP_EXP2: return fb(exp2(f));
-        case OP_LOG1P: return fb(log1p(f));
-        case OP_EXPM1: return fb(expm1(f));
+        // f(-0.0) = -0.0 (C Annex F, numpy): the device library's log1p / expm1 return +0.0
+        case OP_LOG1P: return f == 0.0 ? x : fb(log1p(f));
+        case OP_EXPM1: return f == 0.0 ? x : fb(expm1(f));
         case OP_SIN: return fb(sin(f));
         case OP_COS: return fb(cos(f));
         case OP_TAN: return fb(tan(f));
@@ -155,7 +165,10 @@ template <bool MATH> __device__ inline uint64_t unary(uint32_t op, uint32_t arg,
     switch (op) {
     case OP_I2F: return fb((double)v);
     case OP_U2F: return fb((double)x);
+    case OP_I2F32: return fb((double)(float)v);  // one rounding, int64 -> float32 (numpy's cast)
+    case OP_U2F32: return fb((double)(float)x);
     case OP_F2I: return (uint64_t)(int64_t)f;
+    case OP_F2U: return (uint64_t)f;
     case OP_ROUND_F32: return fb((double)(float)f);
     case OP_WRAP: {
         const uint32_t bits = arg & 0xff, sgn = arg >> 8;
@@ -181,41 +194,12 @@ template <bool MATH> __device__ inline uint64_t unary(uint32_t op, uint32_t arg,
     return x;
 }
 
-template <bool MATH> __device__ inline uint64_t binary(uint32_t op, uint64_t a, uint64_t b) {
+// the comparisons on their own: all that k_expr_terms needs of `binary`, whose division and
+// float32 divmod bodies would otherwise cost that kernel registers (and a wave of occupancy)
+__device__ inline uint64_t compare(uint32_t op, uint64_t a, uint64_t b) {
     const double fa = as_f(a), fbv = as_f(b);
     const int64_t ia = as_i(a), ib = as_i(b);
     switch (op) {
-    case OP_ADD_F: return fb(fa + fbv);
-    case OP_SUB_F: return fb(fa - fbv);
-    case OP_MUL_F: return fb(fa * fbv);
-    case OP_DIV_F: return fb(fa / fbv);
-    case OP_FLOORDIV_F: {
-        double q, r;
-        divmod_f(fa, fbv, &q, &r);
-        return fb(q);
-    }
-    case OP_MOD_F: {
-        double q, r;
-        divmod_f(fa, fbv, &q, &r);
-        return fb(r);
-    }
-    case OP_POW_F: if constexpr (MATH) return fb(pow(fa, fbv)); else return a;
-    case OP_MIN_F: return fb((fa != fa || fbv != fbv) ? (fa != fa ? fa : fbv) : (fa < fbv ? fa : fbv));
-    case OP_MAX_F: return fb((fa != fa || fbv != fbv) ? (fa != fa ? fa : fbv) : (fa > fbv ? fa : fbv));
-    case OP_ARCTAN2: if constexpr (MATH) return fb(atan2(fa, fbv)); else return a;
-    case OP_ADD_I: return a + b;
-    case OP_SUB_I: return a - b;
-    case OP_MUL_I: return a * b;
-    case OP_FLOORDIV_I: return (uint64_t)floordiv_i(ia, ib);
-    case OP_MOD_I: return (uint64_t)mod_i(ia, ib);
-    case OP_AND_I: return a & b;
-    case OP_OR_I: return a | b;
-    case OP_XOR_I: return a ^ b;
-    case OP_MIN_I: return ia < ib ? a : b;
-    case OP_MAX_I: return ia > ib ? a : b;
-    case OP_SHL_I: return (ib < 0 || ib >= 64) ? 0 : a << ib;
-    case OP_SHR_I: return (ib < 0 || ib >= 64) ? (uint64_t)(ia < 0 ? -1 : 0) : (uint64_t)(ia >> ib);
-    case OP_POW_I: return (uint64_t)pow_i(ia, ib);
     case OP_LT_F: return fa < fbv;
     case OP_LE_F: return fa <= fbv;
     case OP_GT_F: return fa > fbv;
@@ -236,10 +220,61 @@ template <bool MATH> __device__ inline uint64_t binary(uint32_t op, uint64_t a, 
     return a;
 }
 
+template <bool MATH> __device__ inline uint64_t binary(uint32_t op, uint64_t a, uint64_t b) {
+    const double fa = as_f(a), fbv = as_f(b);
+    const int64_t ia = as_i(a), ib = as_i(b);
+    switch (op) {
+    case OP_ADD_F: return fb(fa + fbv);
+    case OP_SUB_F: return fb(fa - fbv);
+    case OP_MUL_F: return fb(fa * fbv);
+    case OP_DIV_F: return fb(fa / fbv);
+    case OP_FLOORDIV_F: {
+        double q, r;
+        divmod_f(fa, fbv, &q, &r);
+        return fb(q);
+    }
+    case OP_MOD_F: {
+        double q, r;
+        divmod_f(fa, fbv, &q, &r);
+        return fb(r);
+    }
+    case OP_FLOORDIV_F32: case OP_MOD_F32: {  // float32 operands arrive as exact float64 slots
+        float q, r;
+        divmod_f((float)fa, (float)fbv, &q, &r);
+        return fb((double)(op == OP_FLOORDIV_F32 ? q : r));
+    }
+    case OP_POW_F: if constexpr (MATH) return fb(pow(fa, fbv)); else return a;
+    case OP_MIN_F: return fb((fa != fa || fbv != fbv) ? (fa != fa ? fa : fbv) : (fa < fbv ? fa : fbv));
+    case OP_MAX_F: return fb((fa != fa || fbv != fbv) ? (fa != fa ? fa : fbv) : (fa > fbv ? fa : fbv));
+    case OP_ARCTAN2: if constexpr (MATH) return fb(atan2(fa, fbv)); else return a;
+    case OP_ADD_I: return a + b;
+    case OP_SUB_I: return a - b;
+    case OP_MUL_I: return a * b;
+    case OP_FLOORDIV_I: return (uint64_t)floordiv_i(ia, ib);
+    case OP_MOD_I: return (uint64_t)mod_i(ia, ib);
+    case OP_AND_I: return a & b;
+    case OP_OR_I: return a | b;
+    case OP_XOR_I: return a ^ b;
+    case OP_MIN_I: return ia < ib ? a : b;
+    case OP_MAX_I: return ia > ib ? a : b;
+    case OP_SHL_I: return (ib < 0 || ib >= 64) ? 0 : a << ib;
+    case OP_SHR_I: return (ib < 0 || ib >= 64) ? (uint64_t)(ia < 0 ? -1 : 0) : (uint64_t)(ia >> ib);
+    case OP_POW_I: return (uint64_t)pow_i(ia, ib);
+    // uint64 nodes: a slot at or above 2^63 is not negative
+    case OP_FLOORDIV_U: return b == 0 ? 0 : a / b;  // numpy: 0 (with a warning)
+    case OP_MOD_U: return b == 0 ? 0 : a % b;
+    case OP_MIN_U: return a < b ? a : b;
+    case OP_MAX_U: return a > b ? a : b;
+    case OP_SHR_U: return b >= 64 ? 0 : a >> b;
+    case OP_POW_U: return pow_u(a, b);
+    }
+    return compare(op, a, b);
+}
+
 __host__ __device__ inline bool is_binary(uint32_t op) {
-    return (op >= OP_ADD_F && op <= OP_ARCTAN2 && op != OP_NEG_F && op != OP_ABS_F) ||
+    return (op >= OP_ADD_F && op <= OP_MOD_F32 && op != OP_NEG_F && op != OP_ABS_F) ||
            (op >= OP_ADD_I && op <= OP_POW_I && op != OP_NEG_I && op != OP_ABS_I && op != OP_INV_I) ||
-           (op >= OP_LT_F && op <= OP_GE_U);
+           (op >= OP_LT_F && op <= OP_GE_U) || (op >= OP_FLOORDIV_U && op <= OP_POW_U);
 }
 
 // MATH: the program calls transcendental functions (pow, exp, sin, ...), whose inlined
@@ -316,7 +351,7 @@ __global__ __launch_bounds__(EX_THREADS) void k_expr(ExprProg prog, uint64_t n, 
 // issues each column's loads inside its program step and shifts the register stack per push
 // (`w > 0.4` over 1e9 float64 rows: 7.4 ms, 1.2 TB/s, profiles/r06_filter_tl.txt).  Here each
 // lane takes 8 consecutive rows: a term's column is read with 16-byte loads (8 rows of its
-// dtype), compared with the term's constant by the interpreter's own `binary` / `unary`
+// dtype), compared with the term's constant by the interpreter's own `compare` / `unary`
 // (identical results by construction), folded into the 8 keep bytes, stored as one 8-byte
 // word.  vh_expr_eval recognises the program shape; anything else runs the interpreter.
 constexpr int EX_MAX_TERMS = 8;
@@ -329,36 +364,38 @@ struct ExprTerms {
     int32_t nt, conj, neg;
 };
 
-// 8 consecutive rows' 64-bit slots (load_slot's widening) from 16-byte loads when the column
-// block is aligned and whole, else element by element
+// 8 consecutive rows of a column of T as 64-bit slots (load_slot's widening), from 16-byte loads
+template <typename T> __device__ inline void load_vec8(const char *b, uint64_t (&v)[EXT_RPT]) {
+    struct Words { uint4 u[sizeof(T) * EXT_RPT / 16]; } w;
+    struct Rows { T e[EXT_RPT]; };
+#pragma unroll
+    for (int q = 0; q < (int)(sizeof(T) * EXT_RPT / 16); q++) w.u[q] = reinterpret_cast<const uint4 *>(b)[q];
+    const Rows rows = __builtin_bit_cast(Rows, w);
+#pragma unroll
+    for (int r = 0; r < EXT_RPT; r++) {
+        if constexpr (std::is_floating_point_v<T>) v[r] = fb((double)rows.e[r]);
+        else if constexpr (std::is_signed_v<T>) v[r] = (uint64_t)(int64_t)rows.e[r];
+        else v[r] = (uint64_t)rows.e[r];
+    }
+}
+
+// 8 consecutive rows' 64-bit slots from 16-byte loads when the column block is aligned and
+// whole, else element by element.  One typed body per dtype, not one body that decodes the
+// words by a run-time item size
 __device__ inline void load_slots8(const void *p, int dt, uint64_t base, uint32_t cnt, uint64_t (&v)[EXT_RPT]) {
     const int isz = dt == VH_F64 || dt == VH_I64 || dt == VH_U64 ? 8 : dt == VH_F32 || dt == VH_I32 || dt == VH_U32 ? 4
                   : dt == VH_I16 || dt == VH_U16 ? 2 : 1;
     const char *b = static_cast<const char *>(p) + base * isz;
     if (cnt == EXT_RPT && (reinterpret_cast<uintptr_t>(b) & 15) == 0 && isz >= 2) {
-        uint32_t w[16];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (q * 16 < EXT_RPT * isz) {
-                const uint4 u = reinterpret_cast<const uint4 *>(b)[q];
-                w[4 * q] = u.x;
-                w[4 * q + 1] = u.y;
-                w[4 * q + 2] = u.z;
-                w[4 * q + 3] = u.w;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < EXT_RPT; r++) {
-            uint64_t raw;
-            if (isz == 8) raw = (uint64_t)w[2 * r] | ((uint64_t)w[2 * r + 1] << 32);
-            else if (isz == 4) raw = w[r];
-            else raw = (w[r >> 1] >> (16 * (r & 1))) & 0xffffu;
-            switch (dt) {
-            case VH_F32: v[r] = fb((double)__builtin_bit_cast(float, (uint32_t)raw)); break;
-            case VH_I32: v[r] = (uint64_t)(int64_t)(int32_t)(uint32_t)raw; break;
-            case VH_I16: v[r] = (uint64_t)(int64_t)(int16_t)(uint16_t)raw; break;
-            default: v[r] = raw;  // float64 bits, int64, uint64 / 32 / 16
-            }
+        switch (dt) {
+        case VH_F64: load_vec8<double>(b, v); break;
+        case VH_F32: load_vec8<float>(b, v); break;
+        case VH_I64: load_vec8<int64_t>(b, v); break;
+        case VH_I32: load_vec8<int32_t>(b, v); break;
+        case VH_I16: load_vec8<int16_t>(b, v); break;
+        case VH_U64: load_vec8<uint64_t>(b, v); break;
+        case VH_U32: load_vec8<uint32_t>(b, v); break;
+        default: load_vec8<uint16_t>(b, v); break;  // isz >= 2 leaves VH_U16
         }
         return;
     }
@@ -381,7 +418,7 @@ __global__ __launch_bounds__(EX_THREADS) void k_expr_terms(ExprTerms t, uint64_t
 #pragma unroll
             for (int r = 0; r < EXT_RPT; r++) {
                 const uint64_t x = uc ? unary<false>(uc & 0xff, uc >> 8, v[r]) : v[r];
-                const uint32_t bit = (uint32_t)binary<false>(cop, x, c);
+                const uint32_t bit = (uint32_t)compare(cop, x, c);  // match_terms admits comparisons only
                 acc[r] = t.conj ? (acc[r] & bit) : (acc[r] | bit);
             }
         }

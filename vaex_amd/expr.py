@@ -7,13 +7,25 @@ stack program and evaluates it with one HIP kernel per chunk, writing a new HBM 
 (or a uint8 mask for selections / filters) -- no host round trip.
 
 Semantics follow numpy 2: the result dtype of every node is numpy's own (found by running
-the numpy operation on empty arrays / Python scalars, so NEP 50 weak scalars hold), float32
-nodes are rounded to float32 after each operation and narrow integer nodes wrap, like
-numpy's.  Supported: columns, virtual columns, variables, Python int / float / bool
+the numpy operation on empty arrays / Python scalars, so NEP 50 weak scalars hold: a Python
+constant in a float32 node is converted to float32 before the operation), float32 nodes
+are rounded to float32 after each operation (``//`` and ``%`` run in float32) and narrow
+integer nodes wrap, like numpy's; uint64 nodes run unsigned operations, integers of any two
+dtypes compare exactly (int64 against uint64, a Python int outside the column's dtype), and
+a 64-bit integer becomes float32 in one rounding.  Everything but the transcendental
+functions is numpy's result bit for bit; those are within 4 ulp in float64 (a float32 node:
+the float64 result rounded once), exact where the result is NaN, infinite or zero
+(tests/expr_np.py).  Undefined in numpy and not pinned: float -> integer
+casts of NaN, infinities or values outside the target type, negative shift counts, integer
+``**`` with a negative exponent in a column.
+
+Supported: columns, virtual columns, variables, Python int / float / bool
 constants, ``+ - * / // % **``, unary ``- ~``, comparisons (chained too), ``& | ^ << >>``,
 ``and / or / not`` on booleans, and the functions in :data:`FUNCTIONS` (also as ``np.f``).
 Anything else raises :class:`UnsupportedExpression`, which callers turn into the host path
-or an error (there is no silent fallback for HBM columns).
+or an error (there is no silent fallback for HBM columns); so does what numpy itself refuses
+(a Python int outside the dtype in arithmetic, ``minimum`` / ``maximum``, shifts or
+``where``; dtype pairs without a loop), integers beyond 64 bits and float16 results.
 """
 import ast
 import ctypes
@@ -23,9 +35,9 @@ import numpy as np
 from . import _lib
 
 # opcodes (csrc/expr.hip)
-OP = dict(COL=0, CONST=1, I2F=2, F2I=3, ROUND_F32=4, WRAP=5, U2F=6,
+OP = dict(COL=0, CONST=1, I2F=2, F2I=3, ROUND_F32=4, WRAP=5, U2F=6, I2F32=7, U2F32=8, F2U=9,
           ADD_F=10, SUB_F=11, MUL_F=12, DIV_F=13, FLOORDIV_F=14, MOD_F=15, POW_F=16, NEG_F=17, ABS_F=18,
-          MIN_F=19, MAX_F=20, ARCTAN2=21,
+          MIN_F=19, MAX_F=20, ARCTAN2=21, FLOORDIV_F32=22, MOD_F32=23,
           ADD_I=30, SUB_I=31, MUL_I=32, FLOORDIV_I=33, MOD_I=34, NEG_I=35, ABS_I=36, AND_I=37, OR_I=38,
           XOR_I=39, INV_I=40, MIN_I=41, MAX_I=42, SHL_I=43, SHR_I=44, POW_I=45,
           LT_F=50, LE_F=51, GT_F=52, GE_F=53, EQ_F=54, NE_F=55,
@@ -34,7 +46,14 @@ OP = dict(COL=0, CONST=1, I2F=2, F2I=3, ROUND_F32=4, WRAP=5, U2F=6,
           SQRT=80, EXP=81, LOG=82, LOG10=83, SIN=84, COS=85, TAN=86, ARCSIN=87, ARCCOS=88, ARCTAN=89,
           SINH=90, COSH=91, TANH=92, FLOOR=93, CEIL=94, ISNAN=95, ISFINITE=96, ISINF=97, LOG1P=98, EXPM1=99,
           LOG2=100, EXP2=101, TRUNC=102, RINT=103,
-          WHERE=110)
+          WHERE=110,
+          FLOORDIV_U=120, MOD_U=121, MIN_U=122, MAX_U=123, SHR_U=124, POW_U=125)
+# the opcodes that pop two slots and push one (expr.hip is_binary)
+BINARY = frozenset(OP[k] for k in (
+    "ADD_F SUB_F MUL_F DIV_F FLOORDIV_F MOD_F POW_F MIN_F MAX_F ARCTAN2 FLOORDIV_F32 MOD_F32 "
+    "ADD_I SUB_I MUL_I FLOORDIV_I MOD_I AND_I OR_I XOR_I MIN_I MAX_I SHL_I SHR_I POW_I "
+    "LT_F LE_F GT_F GE_F EQ_F NE_F LT_I LE_I GT_I GE_I EQ_I NE_I LT_U LE_U GT_U GE_U "
+    "FLOORDIV_U MOD_U MIN_U MAX_U SHR_U POW_U").split())
 MAX_CODE, MAX_CONST, MAX_COLS, MAX_DEPTH = 128, 32, 16, 8
 
 # float -> float functions (numpy ufunc, opcode)
@@ -92,10 +111,11 @@ class Compiler:
             bits, dt = int(np.array(float(value)).view(np.uint64)), np.float64
         else:
             raise UnsupportedExpression(f"constant {value!r}")
-        if len(self.consts) >= MAX_CONST:
-            raise UnsupportedExpression("too many constants")
-        self.consts.append(bits)
-        idx = len(self.consts) - 1
+        # the pool may hold constants that no instruction uses in the end (a weak scalar is
+        # re-pushed in the node's dtype): Program drops those and checks MAX_CONST
+        if bits not in self.consts:
+            self.consts.append(bits)
+        idx = self.consts.index(bits)
         return _Typed([OP["CONST"] | idx << 8], dt, scalar=value if not isinstance(value, np.generic) else value.item())
 
     def _column(self, name):
@@ -112,20 +132,40 @@ class Compiler:
         return _Typed([OP["COL"] | self.columns.index(name) << 8], dt)
 
     # ---- conversions -----------------------------------------------------------------
-    @staticmethod
-    def _to_float(t):
-        """code leaving t's value as float64 bits."""
+    def _to_float(self, t, dt):
+        """code leaving t's value as float64 bits, for an operand of a node that numpy
+        computes in the float dtype ``dt``."""
+        dt = np.dtype(dt)
+        if t.scalar is not None:
+            # a weak scalar (NEP 50) is converted to the node's dtype before the operation:
+            # `f32 * 0.1` multiplies by float32(0.1).  numpy does the conversion itself here
+            with np.errstate(all="ignore"):
+                v = float((np.ones(1, dt) * t.scalar)[0])
+            return list(self._const(v).code)
         k = _kind(t.dtype)
         if k == "f":
             return list(t.code)
-        if t.scalar is not None and not isinstance(t.scalar, bool):
-            return list(t.code) + [OP["I2F"]]
-        return list(t.code) + [OP["U2F"] if (k == "u" and t.dtype.itemsize == 8) else OP["I2F"]]
+        wide = t.dtype.itemsize == 8
+        if dt == np.float32 and wide:  # one rounding, as (float)int64: not int -> double -> float
+            return list(t.code) + [OP["U2F32" if k == "u" else "I2F32"]]
+        return list(t.code) + [OP["U2F" if (k == "u" and wide) else "I2F"]]
+
+    @staticmethod
+    def _resolve(fn, *protos):
+        """numpy's result dtype of ``fn(*protos)``; what numpy refuses is UnsupportedExpression
+        (TypeError: no loop for the dtypes; OverflowError: a Python int outside the dtype)."""
+        with np.errstate(all="ignore"):
+            try:
+                return np.result_type(fn(*protos))
+            except (TypeError, OverflowError) as e:
+                raise UnsupportedExpression(str(e))
 
     @staticmethod
     def _finish(code, dtype):
         """the node's own rounding / wrap-around (numpy computes in the result dtype)."""
         dtype = np.dtype(dtype)
+        if dtype.kind == "f" and dtype.itemsize not in (4, 8):
+            raise UnsupportedExpression(f"{dtype} result (numpy computes sqrt(int8), say, in float16)")
         if dtype == np.float32:
             return code + [OP["ROUND_F32"]]
         if dtype.kind in "iu" and dtype.itemsize < 8:
@@ -172,11 +212,7 @@ class Compiler:
     def _arith(self, opname, a, b):
         ufunc = {"+": np.add, "-": np.subtract, "*": np.multiply, "/": np.true_divide, "//": np.floor_divide,
                  "%": np.remainder, "**": np.power}[opname]
-        with np.errstate(all="ignore"):
-            try:
-                dt = np.result_type(ufunc(a.proto, b.proto))
-            except TypeError as e:
-                raise UnsupportedExpression(str(e))
+        dt = self._resolve(ufunc, a.proto, b.proto)
         if a.scalar is not None and b.scalar is not None:
             with np.errstate(all="ignore"):
                 v = ufunc(a.scalar, b.scalar)
@@ -188,7 +224,7 @@ class Compiler:
         if dt.kind == "f" and opname == "**" and b.scalar is not None and a.scalar is None \
                 and not isinstance(b.scalar, bool) and b.scalar in (2, 0.5, -1, 1):
             # numpy's fast_scalar_power: x**2 = square, x**0.5 = sqrt, x**-1 = reciprocal
-            x = self._to_float(a)
+            x = self._to_float(a, dt)
             if b.scalar == 2:
                 code = x + x + [OP["MUL_F"]]
             elif b.scalar == 0.5:
@@ -198,25 +234,31 @@ class Compiler:
             else:
                 code = x
         elif dt.kind == "f":
-            code = self._to_float(a) + self._to_float(b)
-            code.append(OP[{"+": "ADD_F", "-": "SUB_F", "*": "MUL_F", "/": "DIV_F", "//": "FLOORDIV_F",
-                            "%": "MOD_F", "**": "POW_F"}[opname]])
+            code = self._to_float(a, dt) + self._to_float(b, dt)
+            op = {"+": "ADD_F", "-": "SUB_F", "*": "MUL_F", "/": "DIV_F", "//": "FLOORDIV_F", "%": "MOD_F",
+                  "**": "POW_F"}[opname]
+            if dt == np.float32 and opname in ("//", "%"):
+                # + - * / and sqrt in float64, rounded once, equal the float32 operation; the
+                # several steps of floor_divide / remainder do not, so they run in float32
+                op += "32"
+            code.append(OP[op])
         else:
             if opname == "**" and b.scalar is not None and b.scalar < 0:
                 raise UnsupportedExpression("integers to negative integer powers")
             code = a.code + b.code
-            code.append(OP[{"+": "ADD_I", "-": "SUB_I", "*": "MUL_I", "//": "FLOORDIV_I", "%": "MOD_I",
-                            "**": "POW_I"}[opname]])
+            op = {"+": "ADD_I", "-": "SUB_I", "*": "MUL_I", "//": "FLOORDIV_I", "%": "MOD_I", "**": "POW_I"}[opname]
+            if dt == np.uint64 and op in ("FLOORDIV_I", "MOD_I", "POW_I"):
+                op = op[:-1] + "U"  # a slot holds 64 bits: only uint64 nodes can exceed the signed range
+            code.append(OP[op])
         return _Typed(self._finish(code, dt), dt)
 
     def _bitwise(self, opname, a, b):
         ufunc = {"&": np.bitwise_and, "|": np.bitwise_or, "^": np.bitwise_xor,
                  "<<": np.left_shift, ">>": np.right_shift}[opname]
-        try:
-            dt = np.result_type(ufunc(a.proto, b.proto))
-        except TypeError as e:
-            raise UnsupportedExpression(str(e))
+        dt = self._resolve(ufunc, a.proto, b.proto)
         op = {"&": "AND_I", "|": "OR_I", "^": "XOR_I", "<<": "SHL_I", ">>": "SHR_I"}[opname]
+        if dt == np.uint64 and op == "SHR_I":
+            op = "SHR_U"
         return _Typed(self._finish(a.code + b.code + [OP[op]], dt), dt)
 
     def v_BinOp(self, node):
@@ -250,15 +292,56 @@ class Compiler:
             return _Typed(self._finish(a.code + [OP["INV_I"]], a.dtype), a.dtype)
         raise UnsupportedExpression("unary operator")
 
+    _MIRROR = {"LT": "GT", "LE": "GE", "GT": "LT", "GE": "LE", "EQ": "EQ", "NE": "NE"}
+
     def _compare(self, op, a, b):
-        dt = np.result_type(a.proto, b.proto)
         sym = {ast.Lt: "LT", ast.LtE: "LE", ast.Gt: "GT", ast.GtE: "GE", ast.Eq: "EQ", ast.NotEq: "NE"}.get(type(op))
         if sym is None:
             raise UnsupportedExpression("comparison operator")
+
+        def is_int(t):
+            return t.scalar is not None and not isinstance(t.scalar, bool) and isinstance(t.scalar, int)
+
+        # integers compare exactly in numpy 2, whatever the two dtypes
+        if is_int(b) and a.scalar is None and a.dtype.kind in "iub":
+            return self._compare_int_const(sym, a, b)
+        if is_int(a) and b.scalar is None and b.dtype.kind in "iub":
+            return self._compare_int_const(self._MIRROR[sym], b, a)
+        if a.scalar is None and b.scalar is None and {a.dtype.kind, b.dtype.kind} == {"i", "u"} \
+                and np.uint64 in (a.dtype, b.dtype):
+            if a.dtype.kind == "i":
+                return self._compare_signed_unsigned(sym, a, b)
+            return self._compare_signed_unsigned(self._MIRROR[sym], b, a)
+        dt = self._resolve(np.result_type, a.proto, b.proto)
         if dt.kind == "f":
-            return _Typed(self._to_float(a) + self._to_float(b) + [OP[sym + "_F"]], np.bool_)
-        unsigned = dt.kind == "u" and dt.itemsize == 8 and sym not in ("EQ", "NE")
+            return _Typed(self._to_float(a, dt) + self._to_float(b, dt) + [OP[sym + "_F"]], np.bool_)
+        unsigned = dt == np.uint64 and sym not in ("EQ", "NE")
         return _Typed(a.code + b.code + [OP[sym + ("_U" if unsigned else "_I")]], np.bool_)
+
+    def _compare_int_const(self, sym, col, con):
+        """``col sym con`` for an integer / boolean column expression and a Python int, which
+        may lie outside the column's dtype: numpy 2 answers as if both were exact integers."""
+        v = con.scalar
+        if col.dtype.kind == "b" and not -(1 << 63) <= v < (1 << 63):
+            raise UnsupportedExpression("boolean compared with an integer outside int64")  # numpy raises
+        if col.dtype == np.uint64:
+            if v < 0:  # every value is greater
+                return _Typed(self._const(sym in ("GT", "GE", "NE")).code, np.bool_)
+            return _Typed(col.code + con.code + [OP[sym + ("_I" if sym in ("EQ", "NE") else "_U")]], np.bool_)
+        # any other slot is a sign- / zero-extended value within int64
+        if v >= (1 << 63):  # every value is less
+            return _Typed(self._const(sym in ("LT", "LE", "NE")).code, np.bool_)
+        return _Typed(col.code + con.code + [OP[sym + "_I"]], np.bool_)
+
+    def _compare_signed_unsigned(self, sym, s, u):
+        """``s sym u`` for a signed expression and a uint64 one, exactly (numpy 2 does not go
+        through float64 here): a negative s is below every u, otherwise both compare unsigned."""
+        zero = self._const(0).code
+        if sym in ("LT", "LE", "NE"):
+            first, second, comb = "LT_I", sym + ("_I" if sym == "NE" else "_U"), "OR_I"
+        else:
+            first, second, comb = "GE_I", sym + ("_I" if sym == "EQ" else "_U"), "AND_I"
+        return _Typed(s.code + zero + [OP[first]] + s.code + u.code + [OP[second], OP[comb]], np.bool_)
 
     def v_Compare(self, node):
         left = self.visit(node.left)
@@ -296,10 +379,10 @@ class Compiler:
         if name in FUNCTIONS and len(args) == 1:
             ufunc, op = FUNCTIONS[name]
             a = args[0]
-            dt = np.result_type(ufunc(a.proto))
+            dt = self._resolve(ufunc, a.proto)
             if dt.kind != "f":
                 raise UnsupportedExpression(f"{name} of {a.dtype}")
-            return _Typed(self._finish(self._to_float(a) + [OP[op]], dt), dt)
+            return _Typed(self._finish(self._to_float(a, dt) + [OP[op]], dt), dt)
         if name in PREDICATES and len(args) == 1:
             a = args[0]
             if a.dtype.kind != "f":  # integers are never nan / inf: a constant column
@@ -308,27 +391,34 @@ class Compiler:
         if name in ("abs", "absolute", "fabs") and len(args) == 1:
             a = args[0]
             if a.dtype.kind == "f" or name == "fabs":
-                dt = np.result_type(np.fabs(a.proto)) if name == "fabs" else a.dtype
-                return _Typed(self._finish(self._to_float(a) + [OP["ABS_F"]], dt), dt)
+                dt = self._resolve(np.fabs, a.proto) if name == "fabs" else a.dtype
+                return _Typed(self._finish(self._to_float(a, dt) + [OP["ABS_F"]], dt), dt)
+            if a.dtype.kind in "ub":  # the identity; ABS_I would read a uint64 >= 2**63 as negative
+                return a
             return _Typed(self._finish(a.code + [OP["ABS_I"]], a.dtype), a.dtype)
         if name in ("minimum", "maximum", "fmin", "fmax", "arctan2") and len(args) == 2:
             a, b = args
-            ufunc = getattr(np, name)
-            dt = np.result_type(ufunc(a.proto, b.proto))
             if name in ("fmin", "fmax"):
                 raise UnsupportedExpression(name)
+            dt = self._resolve(getattr(np, name), a.proto, b.proto)
             if dt.kind == "f":
                 op = {"minimum": "MIN_F", "maximum": "MAX_F", "arctan2": "ARCTAN2"}[name]
-                return _Typed(self._finish(self._to_float(a) + self._to_float(b) + [OP[op]], dt), dt)
-            op = {"minimum": "MIN_I", "maximum": "MAX_I"}[name]
+                return _Typed(self._finish(self._to_float(a, dt) + self._to_float(b, dt) + [OP[op]], dt), dt)
+            if name == "arctan2":
+                raise UnsupportedExpression(f"arctan2 of {dt}")
+            op = {"minimum": "MIN", "maximum": "MAX"}[name] + ("_U" if dt == np.uint64 else "_I")
             return _Typed(self._finish(a.code + b.code + [OP[op]], dt), dt)
         if name == "where" and len(args) == 3:
             c, a, b = args
             if c.dtype.kind != "b":
                 raise UnsupportedExpression("where condition must be boolean")
-            dt = np.result_type(np.where(np.empty(0, bool), a.proto, b.proto))
+            dt = self._resolve(np.where, np.empty(0, bool), a.proto, b.proto)
+            for t in (a, b):  # np.where wraps such a value silently; every other operation refuses it
+                if dt.kind in "iu" and isinstance(t.scalar, int) and not isinstance(t.scalar, bool) \
+                        and not np.iinfo(dt).min <= t.scalar <= np.iinfo(dt).max:
+                    raise UnsupportedExpression(f"Python integer {t.scalar} out of bounds for {dt}")
             if dt.kind == "f":
-                code = c.code + self._to_float(a) + self._to_float(b) + [OP["WHERE"]]
+                code = c.code + self._to_float(a, dt) + self._to_float(b, dt) + [OP["WHERE"]]
             else:
                 code = c.code + a.code + b.code + [OP["WHERE"]]
             return _Typed(self._finish(code, dt), dt)
@@ -350,22 +440,26 @@ class Compiler:
         if a.dtype == dt and a.scalar is None:
             return a
         if a.scalar is not None:
+            # numpy's result is a scalar of dtype dt: strong in promotion, unlike a Python scalar
+            # (`f32 + astype(0.1, 'float64')` is float64), so the constant keeps dt and no scalar
+            self._finish([], dt)  # refuses float16
             with np.errstate(all="ignore"):
-                return self._const(np.array(a.scalar).astype(dt).item())
+                return _Typed(self._const(np.array(a.scalar).astype(dt).item()).code, dt)
         if dt.kind == "f":
-            return _Typed(self._finish(self._to_float(a), dt), dt)
+            return _Typed(self._finish(self._to_float(a, dt), dt), dt)
         if dt.kind == "b":
             if a.dtype.kind == "f":
-                code = self._to_float(a) + self._const(0.0).code + [OP["NE_F"]]
+                code = list(a.code) + self._const(0.0).code + [OP["NE_F"]]
             else:
                 code = a.code + self._const(0).code + [OP["NE_I"]]
             return _Typed(code, dt)
-        code = list(a.code) + ([OP["F2I"]] if a.dtype.kind == "f" else [])
+        # float -> uint64 reaches 2**64, beyond F2I's int64
+        code = list(a.code) + ([OP["F2U" if dt == np.uint64 else "F2I"]] if a.dtype.kind == "f" else [])
         return _Typed(self._finish(code, dt), dt)
 
 
 def _stack_depth(code):
-    binary = set(range(10, 22)) - {17, 18} | (set(range(30, 46)) - {35, 36, 40}) | set(range(50, 70))
+    binary = BINARY
     d = m = 0
     for ins in code:
         op = ins & 0xFF
@@ -395,8 +489,17 @@ class Program:
             raise UnsupportedExpression("expression too long for the device program")
         if _stack_depth(code) > MAX_DEPTH:
             raise UnsupportedExpression("expression too deeply nested")
+        # keep the constants that the program uses, in the order of first use
+        used = []
+        for k, ins in enumerate(code):
+            if ins & 0xFF == OP["CONST"]:
+                if ins >> 8 not in used:
+                    used.append(ins >> 8)
+                code[k] = OP["CONST"] | used.index(ins >> 8) << 8
+        if len(used) > MAX_CONST:
+            raise UnsupportedExpression("too many constants")
         self.code = code
-        self.consts = list(c.consts)
+        self.consts = [c.consts[k] for k in used]
         self.columns = list(c.columns)
         self.dtype = t.dtype  # bool results are 0 / 1 bytes (numpy bool)
         self.is_bool = t.dtype.kind == "b"
