@@ -72,6 +72,7 @@ typedef struct vh_binner vh_binner;
 typedef struct vh_grid vh_grid;
 typedef struct vh_agg vh_agg;
 typedef struct vh_set vh_set;
+typedef struct vh_counter vh_counter;
 
 /* ---- library / device plumbing ---------------------------------------- */
 const char *vh_last_error(void);
@@ -228,6 +229,29 @@ int vh_set_key_array(vh_set *set, void *out_host);
 /* map_ordinal(keys) hash_primitives.hpp:543-583: out_itemsize 1/2/4/8; -1 = unknown key */
 int vh_set_map_ordinal(vh_set *set, const void *keys, uint64_t n, int loc, void *out, int out_itemsize,
                        int out_loc);
+
+/* ---- counter_<dtype>: hash_primitives.hpp:328-415 (key -> occurrence count) ------------ */
+/* Key identity is the ordered set's: one NaN entry, one null entry (mask byte set), every
+ * other key by bit pattern.  initial_capacity: slots of the first table (a power of two
+ * >= 16), 0 = the default; the table grows as needed and a chunk is never counted twice. */
+int vh_counter_create(int dtype, uint64_t initial_capacity, vh_counter **out);
+int vh_counter_destroy(vh_counter *counter);
+/* update(keys[, mask]): every row counts 1.  mask may be NULL (1 = missing); select may be
+ * NULL, rows with select[i] == 0 are not seen at all (as vh_set_update_selected) */
+int vh_counter_update(vh_counter *counter, const void *keys, const uint8_t *mask, const uint8_t *select, uint64_t n,
+                      int loc);
+/* row i adds counts[i] (> 0; rows with 0 are skipped): counter::merge and un-pickling */
+int vh_counter_add(vh_counter *counter, const void *keys, const uint8_t *mask, const int64_t *counts, uint64_t n,
+                   int loc);
+/* length = distinct regular keys + (nan_count > 0) + (null_count > 0) */
+int vh_counter_info(vh_counter *counter, int64_t *length, int64_t *nan_count, int64_t *null_count);
+/* The finish on the device.  order 0: NaN (index 0), null (next index), then the regular
+ * keys ascending (-0.0 before 0.0); 1: that list stably sorted by count ascending; 2: the
+ * exact reverse of 1.  dropnan / dropmissing leave the NaN / null entry out.  keys_out (key
+ * dtype) and counts_out are host arrays of `length` items; n_out items are written.  The
+ * null entry's key is 0 and its index is *null_index (-1 when absent). */
+int vh_counter_read(vh_counter *counter, int order, int dropnan, int dropmissing, void *keys_out, int64_t *counts_out,
+                    uint64_t *n_out, int64_t *null_index);
 
 /* ---- limits pre-pass: vaexfast.cpp:1043-1055 (op_min_max) --------------- */
 int vh_minmax(const void *data, uint64_t n, int dtype, int flip_endian, const uint8_t *mask, int loc,

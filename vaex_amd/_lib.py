@@ -89,6 +89,12 @@ SIGNATURES = {
     "vh_set_info": (_i32, [_vp, _p(_i64), _p(_i64), _p(_i64), _p(_i64), _p(_i64)]),
     "vh_set_key_array": (_i32, [_vp, _vp]),
     "vh_set_map_ordinal": (_i32, [_vp, _vp, _u64, _i32, _vp, _i32, _i32]),
+    "vh_counter_create": (_i32, [_i32, _u64, _p(_vp)]),
+    "vh_counter_destroy": (_i32, [_vp]),
+    "vh_counter_update": (_i32, [_vp, _vp, _vp, _vp, _u64, _i32]),
+    "vh_counter_add": (_i32, [_vp, _vp, _vp, _vp, _u64, _i32]),
+    "vh_counter_info": (_i32, [_vp, _p(_i64), _p(_i64), _p(_i64)]),
+    "vh_counter_read": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _p(_u64), _p(_i64)]),
     "vh_minmax": (_i32, [_vp, _u64, _i32, _i32, _vp, _i32, _p(_dbl), _p(_dbl)]),
     "vh_minmax_sample": (_i32, [_vp, _u64, _i32, _u64, _p(_dbl), _p(_dbl)]),
     "vh_hashagg_create": (_i32, [_i32, _i32, _p(_i32), ctypes.c_uint32, _p(_vp)]),

@@ -5,7 +5,8 @@ path -- ``count/sum/mean/min/max/std/var/first`` (``:741-1000``), ``minmax``
 (``:1276-1333``), ``median_approx`` / ``percentile_approx`` (``:1399-1555``),
 ``cov`` / ``covar`` / ``correlation`` (``:1067-1272``), ``mutual_information``
 (``:622-718``), ``limits`` (``:1617+``), ``_binner*``/``_create_binners``
-(``:5251-5295``), ``_agg``, ``_set`` (``:474``), ``categorize`` (``:5487-5533``),
+(``:5251-5295``), ``_agg``, ``_set`` (``:474``), ``categorize`` (``:5487-5533``), ``unique`` (``:542-619``; with
+``Expression.value_counts`` / ``unique`` / ``nunique``, ``expression.py:946-1093``),
 ``groupby``/``binby`` (``:6622-6683``) and the binner specs ``BinnerScalar`` /
 ``BinnerOrdinal`` (``:6737-6800``) -- over columns that are numpy arrays (staged to
 HBM per chunk) or :class:`~vaex_amd.device.DeviceArray` (HBM-resident).
@@ -22,7 +23,7 @@ from . import agg as vagg
 from .device import DeviceArray
 from .execution import default_executor
 from .promise import Promise, delayed
-from .tasks import TaskMinMax, TaskSetCreate
+from .tasks import TaskMinMax, TaskSetCreate, TaskValueCounts
 from .utils import _expand_limits, _expand_shape, listify, unlistify
 
 default_shape = 128
@@ -151,6 +152,27 @@ class Expression:
     def std(self, *args, **kw): return self.df.std(self.expression, *args, **kw)
     def var(self, *args, **kw): return self.df.var(self.expression, *args, **kw)
     def minmax(self, *args, **kw): return self.df.minmax(self.expression, *args, **kw)
+
+    def value_counts(self, dropna=False, dropnan=False, dropmissing=False, ascending=False, progress=False, axis=None):
+        """expression.py:946-1061: a pandas Series of the counts of the unique values, most
+        frequent first (``ascending=False``); a missing entry is labelled "missing" and comes
+        first.  NaN and missing values are reported unless dropped (pandas drops them)."""
+        return self.df.value_counts(self.expression, dropna=dropna, dropnan=dropnan, dropmissing=dropmissing,
+                                    ascending=ascending, progress=progress, axis=axis)
+
+    def unique(self, dropna=False, dropnan=False, dropmissing=False, selection=None, axis=None, array_type="list",
+               delay=False):
+        """expression.py:1064-1073."""
+        return self.df.unique(self.expression, dropna=dropna, dropnan=dropnan, dropmissing=dropmissing,
+                              selection=selection, array_type=array_type, axis=axis, delay=delay)
+
+    def nunique(self, dropna=False, dropnan=False, dropmissing=False, selection=None, axis=None, delay=False):
+        """expression.py:1075-1093: ``len(df.x.unique()) == df.x.nunique()``."""
+        keys = self.unique(dropna=dropna, dropnan=dropnan, dropmissing=dropmissing, selection=selection, axis=axis,
+                           array_type=None, delay=delay)
+        if isinstance(keys, Promise):
+            return keys.then(len)
+        return len(keys)
 
 
 def _ordinal_values(x, ordered_set):
@@ -836,6 +858,92 @@ class DataFrame:
         task = self.executor.schedule(TaskSetCreate(self, str(expression), unique_limit=unique_limit,
                                                     selection=selection))
         return self._delay(delay, task)
+
+    def _key_dtype(self, expression):
+        """The dtype an expression's set / counter keys are handed back as (datetimes are
+        hashed as int64)."""
+        dt = self.data_type(expression)
+        return dt.newbyteorder("=") if dt.byteorder not in "<=|" else dt
+
+    def value_counts(self, expression, dropna=False, dropnan=False, dropmissing=False, ascending=False, progress=False,
+                     axis=None, selection=None, delay=False):
+        """Expression.value_counts (expression.py:946-1061) over the GPU counter: the column is
+        counted in one pass and the drop / sort-by-count finish runs on the device."""
+        from pandas import Series
+        if axis is not None:
+            raise ValueError("only axis=None is supported")
+        if dropna:
+            dropnan = dropmissing = True
+        expression = _ensure_string(expression)
+        dtype = self._key_dtype(expression)
+        task = self.executor.schedule(TaskValueCounts(self, expression, selection=selection))
+
+        @delayed
+        def finish(counter):
+            keys, counts, null_index = counter.sorted_counts(ascending=ascending, dropnan=dropnan,
+                                                             dropmissing=dropmissing)
+            if dtype.kind in "mM":
+                keys = keys.view(dtype)
+            if null_index < 0:
+                # no missing entry: the index keeps the key dtype (through keys.tolist(), as the
+                # reference builds it, a call took 150 ms at 1e6 keys; the labels are the same)
+                return Series(counts, index=keys, dtype=np.int64)
+            labels = list(keys) if dtype.kind in "mM" else keys.tolist()
+            counts = counts.tolist()
+            labels.pop(null_index)  # expression.py:1052-1059: the missing entry goes first
+            labels = ["missing"] + labels
+            counts = [counts.pop(null_index)] + counts
+            return Series(counts, index=labels, dtype=np.int64)
+
+        return self._delay(delay, finish(task))
+
+    def unique(self, expression, return_inverse=False, dropna=False, dropnan=False, dropmissing=False, progress=False,
+               selection=None, axis=None, delay=False, array_type="python"):
+        """dataframe.py:542-619 over the GPU ordered set: the unique values in first-appearance
+        order; the missing entry is masked unless dropped.  return_inverse: also the ordinal of
+        every (unfiltered) row in the set, ``null_value`` for masked rows."""
+        if dropna:
+            dropnan = dropmissing = True
+        if axis is not None:
+            raise ValueError("only axis=None is supported")
+        if array_type not in ("python", "list", "numpy", None):
+            raise ValueError(f"unknown array_type {array_type!r}")
+        expression = _ensure_string(expression)
+        dtype = self._key_dtype(expression)
+        task = self._set(expression, progress=progress, selection=selection, flatten=axis is None, delay=True)
+
+        @delayed
+        def finish(ordered_set):
+            keys = ordered_set.key_array()
+            if dtype.kind in "mM":
+                keys = keys.view(dtype)
+            deletes = []  # dataframe.py:598-614
+            if dropmissing and ordered_set.has_null:
+                deletes.append(ordered_set.null_value)
+            if dropnan and ordered_set.has_nan:
+                deletes.append(ordered_set.nan_value)
+            if not dropmissing and ordered_set.has_null:
+                # masked before the NaN ordinal is deleted, so the mask stays on the null entry
+                mask = np.zeros(len(keys), dtype=bool)
+                mask[ordered_set.null_value] = True
+                keys = np.ma.array(np.delete(keys, deletes), mask=np.delete(mask, deletes))
+            else:
+                keys = np.delete(keys, deletes)
+            if array_type in ("python", "list"):
+                keys = keys.tolist()
+            if not return_inverse:
+                return keys
+            # dataframe.py:563-578: map_ordinal over every row of the frame
+            values = self.evaluate(expression, filtered=False)
+            if isinstance(values, DeviceArray):
+                inverse = ordered_set.map_ordinal(values).to_numpy().astype(np.int64)
+            else:
+                inverse = ordered_set.map_ordinal(values).astype(np.int64)
+                if np.ma.isMaskedArray(values):
+                    inverse[np.ma.getmaskarray(values)] = ordered_set.null_value
+            return keys, inverse
+
+        return self._delay(delay, finish(task))
 
     # ---- groupby -----------------------------------------------------------------
     def groupby(self, by=None, agg=None, sort=False, assume_sparse="auto", row_limit=None, copy=True,

@@ -19,8 +19,8 @@ import threading
 import numpy as np
 
 from .device import DeviceArray
-from .tasks import TaskAggregation, TaskAggregations, TaskMinMax, TaskSetCreate
-from .taskparts import TaskPartAggregation, TaskPartMinMax, TaskPartSetCreate
+from .tasks import TaskAggregation, TaskAggregations, TaskMinMax, TaskSetCreate, TaskValueCounts
+from .taskparts import TaskPartAggregation, TaskPartMinMax, TaskPartSetCreate, TaskPartValueCounts
 
 # rows per task pass over host (memory-mapped / numpy) columns: each pass is one bin() call,
 # inside which the library double-buffers 16 Mi-row pipe chunks (copy of chunk i+1 under the
@@ -104,6 +104,8 @@ class ExecutorLocal:
                                      task.selection)
         if isinstance(task, TaskMinMax):
             return TaskPartMinMax(df, task.expression, task.selection)
+        if isinstance(task, TaskValueCounts):
+            return TaskPartValueCounts(df, task.expression, df.data_type(task.expression), task.selection)
         raise TypeError(f"unknown task {task!r}")
 
     def execute(self):

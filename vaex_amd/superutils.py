@@ -5,7 +5,8 @@ bindings ``hash_primitives.cpp:26-73``): ``update``, ``key_array``, ``map_ordina
 ``isin``, ``merge``, ``seal``, ``nan_count``/``null_count``/``has_nan``/``has_null``,
 ``nan_value``/``null_value``, ``fingerprint``, ``len()``, the ``create`` constructor
 ``ordered_set_<t>(keys, null_value, nan_count, null_count, fingerprint)`` and
-``flatten_values``.
+``flatten_values``.  ``counter_<dtype>`` (``hash_primitives.hpp:328-415``), the key -> count map
+of ``value_counts``, sits beside it over the library's hash counter.
 
 Ordinals are assigned in first-appearance order over all ``update`` calls -- what a
 single-threaded reference ``update`` with ``nmaps = 1`` produces.  (With threads the
@@ -179,14 +180,175 @@ class _OrderedSetBase:
             self._handle = None
 
 
+# slots of the LDS table a workgroup counts into (counter.hip CT_LT)
+COUNTER_LDS_SLOTS = 8192
+
+
+class _CounterBase:
+    """``counter_<dtype>`` (``hash_primitives.hpp:328-415``; bindings ``hash_primitives.cpp``
+    ``init_hash_``): key -> occurrence count over the GPU hash counter of libvaexhip.
+
+    ``key_array()`` and ``counts()`` are in key order: NaN at index 0 when present, the null
+    entry next (``key_offset``, hash_primitives.hpp:338-348), then the regular keys ascending
+    (the reference's order is its hash maps' iteration order; value_counts sorts by count).
+    ``counter_<t>(keys, counts, null_index)`` rebuilds one (``__reduce__``);
+    ``counter_<t>(initial_capacity=16)`` starts the table at 16 slots."""
+    _dtype = "int64"
+
+    def __init__(self, *args, initial_capacity=0):
+        h = ctypes.c_void_p()
+        if len(args) == 1 and isinstance(args[0], (int, np.integer)):
+            args = ()  # counter(nmaps): one table on the GPU
+        _lib.call("vh_counter_create", _lib.DTYPE_CODE[self._dtype], int(initial_capacity), ctypes.byref(h))
+        self._handle = h.value
+        if len(args) >= 2:
+            keys, counts = args[:2]
+            null_index = args[2] if len(args) > 2 else -1
+            keys = np.asarray(keys, dtype=self._dtype)
+            mask = None
+            if null_index is not None and null_index >= 0:
+                mask = np.zeros(len(keys), np.uint8)
+                mask[int(null_index)] = 1
+            self._add(keys, mask, counts)
+
+    # ---- building --------------------------------------------------------------
+    def update(self, ar, *args, **kwargs):
+        """update(keys[, mask], select=None): rows where select == 0 are not seen at all."""
+        mask = None
+        rest = list(args)
+        if rest and (isinstance(rest[0], (np.ndarray, list, DeviceArray)) or rest[0] is None):
+            mask = rest.pop(0)
+        mask = kwargs.pop("mask", mask)
+        select = kwargs.pop("select", None)
+        if np.ma.isMaskedArray(ar):
+            m = np.ma.getmaskarray(ar)
+            mask = m if mask is None else (np.asarray(mask, bool) | m)
+            ar = ar.data
+        if not isinstance(ar, DeviceArray):
+            ar = np.ascontiguousarray(ar, dtype=self._dtype)
+        device = isinstance(ar, DeviceArray)
+        if device and ar.dtype.itemsize != np.dtype(self._dtype).itemsize:
+            raise TypeError(f"counter_{self._dtype} cannot take a {ar.dtype} column")
+        kptr, n, _, _, loc, keep = _column(ar)
+        mkeep, mptr = self._side(mask, device)
+        skeep, sptr = self._side(select, device)
+        if n:
+            _lib.call("vh_counter_update", self._handle, kptr, mptr, sptr, n, loc)
+
+    @staticmethod
+    def _side(a, device):
+        """A mask / select column where the keys are: (object kept alive, pointer)."""
+        if a is None:
+            return None, None
+        if device:
+            if not isinstance(a, DeviceArray):
+                a = DeviceArray.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
+            return a, a.ptr
+        if isinstance(a, DeviceArray):
+            a = a.to_numpy()
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        return a, a.ctypes.data
+
+    def _add(self, keys, mask, counts):
+        keys = np.ascontiguousarray(keys, dtype=self._dtype)
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        if len(keys) != len(counts):
+            raise ValueError("keys and counts differ in length")
+        mkeep, mptr = self._side(mask, False)
+        if len(keys):
+            _lib.call("vh_counter_add", self._handle, keys.ctypes.data, mptr, counts.ctypes.data, len(keys), _lib.LOC_HOST)
+
+    def merge(self, other):
+        """counter::merge (hash_primitives.hpp:394-415): add every count of ``other``."""
+        keys, counts, null_index = other._read(0, False, False)
+        mask = None
+        if null_index >= 0:
+            mask = np.zeros(len(keys), np.uint8)
+            mask[null_index] = 1
+        self._add(keys, mask, counts)
+
+    # ---- reading ---------------------------------------------------------------
+    def _info(self):
+        vals = [ctypes.c_int64() for _ in range(3)]
+        _lib.call("vh_counter_info", self._handle, *[ctypes.byref(v) for v in vals])
+        return [v.value for v in vals]
+
+    def __len__(self):
+        return self._info()[0]
+
+    def length(self):
+        return len(self)
+
+    nan_count = property(lambda self: self._info()[1])
+    null_count = property(lambda self: self._info()[2])
+    has_nan = property(lambda self: self._info()[1] > 0)
+    has_null = property(lambda self: self._info()[2] > 0)
+
+    def _read(self, order, dropnan, dropmissing):
+        n = len(self)
+        keys = np.empty(n, dtype=self._dtype)
+        counts = np.empty(n, dtype=np.int64)
+        n_out, null_index = ctypes.c_uint64(), ctypes.c_int64(-1)
+        _lib.call("vh_counter_read", self._handle, int(order), int(bool(dropnan)), int(bool(dropmissing)),
+                  keys.ctypes.data, counts.ctypes.data, ctypes.byref(n_out), ctypes.byref(null_index))
+        return keys[:n_out.value], counts[:n_out.value], null_index.value
+
+    def key_array(self):
+        return self._read(0, False, False)[0]
+
+    def counts(self):
+        return self._read(0, False, False)[1]
+
+    @property
+    def null_index(self):
+        """Index of the null entry in key_array() / counts(), -1 when absent."""
+        return int(self.has_nan) if self.has_null else -1
+
+    def extract(self):
+        """{regular key: count} (hash_base::extract)."""
+        keys, counts, _ = self._read(0, True, True)
+        return dict(zip(keys.tolist(), counts.tolist()))
+
+    def sorted_counts(self, ascending=False, dropnan=False, dropmissing=False):
+        """The device finish of value_counts: (keys, counts, null_index) with the NaN / null
+        entries dropped as asked and the rest stably sorted by count (ascending), or the exact
+        reverse of that (expression.py:1026-1050); only the answer crosses the host link."""
+        return self._read(1 if ascending else 2, dropnan, dropmissing)
+
+    def __sizeof__(self):
+        return len(self) * 16
+
+    def __reduce__(self):
+        keys, counts, null_index = self._read(0, False, False)
+        return (type(self), (keys, counts, null_index))
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h:
+            try:
+                _lib.call("vh_counter_destroy", h)
+            except Exception:
+                pass
+            self._handle = None
+
+
 def _register():
     ns = globals()
     for dtype in DTYPES:
         name = "ordered_set_" + dtype
         ns[name] = type(name, (_OrderedSetBase,), {"_dtype": dtype, "__module__": __name__})
+        name = "counter_" + dtype
+        ns[name] = type(name, (_CounterBase,), {"_dtype": dtype, "__module__": __name__})
 
 
 _register()
+
+
+def counter_type_from_dtype(dtype, transient=True):
+    """vaex.hash.counter_type_from_dtype for primitive dtypes (datetimes count as int64)."""
+    dt = np.dtype(dtype)
+    name = "int64" if dt.kind in "mM" else dt.newbyteorder("=").name
+    return globals()["counter_" + name]
 
 
 def ordered_set_type_from_dtype(dtype):

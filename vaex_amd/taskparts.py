@@ -266,6 +266,54 @@ class TaskPartSetCreate:
         return self.set
 
 
+class TaskPartValueCounts:
+    """The map of Expression.value_counts (expression.py:979-993) over a GPU counter: one
+    part shared by all chunks (see_all)."""
+
+    def __init__(self, df, expression, dtype, selection=None):
+        from .superutils import counter_type_from_dtype
+        self.df = df
+        self.expression = expression
+        self.expressions = [expression]
+        self.selection = selection
+        self.counter = counter_type_from_dtype(dtype)()
+
+    def process(self, thread_index, i1, i2, filter_mask, blocks):
+        ar = blocks[self.expression]
+        if isinstance(filter_mask, DeviceArray) or (isinstance(ar, DeviceArray) and self.selection):
+            # HBM frame: filter & selection as one device mask, the counter skips the other rows
+            keep = self.df.device_keep_mask(i1, i2, self.selection or None)
+            if len(ar) == 0:
+                return
+            if isinstance(ar, DeviceArray):
+                self.counter.update(ar, select=keep)
+            else:  # a host (maybe masked) column of an HBM frame: counted where the mask is
+                data, mask = _split_masked(ar)
+                data = DeviceArray.from_numpy(_prepare(data))
+                self.counter.update(data, mask, select=keep)
+            return
+        if self.selection:
+            sel = self.df.evaluate_selection_mask(self.selection, i1=i1, i2=i2, filter_mask=filter_mask)
+            if isinstance(sel, DeviceArray):
+                sel = sel.to_numpy()
+            if isinstance(ar, DeviceArray):
+                ar = ar.to_numpy()
+            ar = ar[np.asarray(sel, dtype=bool)]
+        if len(ar) == 0:
+            return
+        if isinstance(ar, DeviceArray) or np.ma.isMaskedArray(ar):
+            self.counter.update(ar)
+        else:
+            self.counter.update(_prepare(ar))
+
+    def reduce(self, others):
+        for o in others:
+            self.counter.merge(o.counter)
+
+    def get_result(self):
+        return self.counter
+
+
 class TaskPartMinMax:
     """The limits pre-pass on the GPU: NaN-ignoring min/max (vaexfast.cpp:1043-1055,
     tasks.py:173-185 reduce with nanmin/nanmax)."""

@@ -1,7 +1,8 @@
 """Task shapes of the binning path (``packages/vaex-core/vaex/tasks.py``).
 
 ``TaskAggregation`` / ``TaskAggregations`` (tasks.py:331-428), ``TaskSetCreate``
-(tasks.py:98-118) and the min/max limits task (``TaskStatistic`` with ``OP_MIN_MAX``,
+(tasks.py:98-118), ``TaskValueCounts`` (the map / reduce of ``Expression.value_counts``,
+expression.py:977-1000, as a task) and the min/max limits task (``TaskStatistic`` with ``OP_MIN_MAX``,
 tasks.py:149-328).  Tasks are promises fulfilled by :class:`~vaex_amd.execution.ExecutorLocal`.
 """
 from .promise import Promise
@@ -58,6 +59,18 @@ class TaskSetCreate(Task):
         super().__init__(df, [expression], pre_filter=df.filtered)
         self.expression = expression
         self.unique_limit = unique_limit
+        self.selection = selection
+
+
+class TaskValueCounts(Task):
+    """Count the occurrences of an expression's values into a GPU counter
+    (expression.py:977-1000); see_all: one part."""
+
+    see_all = True
+
+    def __init__(self, df, expression, selection=None):
+        super().__init__(df, [expression], pre_filter=df.filtered)
+        self.expression = expression
         self.selection = selection
 
 
