@@ -395,3 +395,56 @@ def test_combine_keys(dtypes):
               (ctypes.c_int * k)(*[_lib.dtype_code(np.dtype(d))[0] for d in dtypes]),
               (ctypes.c_int64 * k)(*mins), (ctypes.c_int64 * k)(*mults), out.ptr)
     np.testing.assert_array_equal(out.to_numpy(), expect)
+
+
+def _fmix32(h):
+    h = h.astype(np.uint32)
+    h ^= h >> np.uint32(16)
+    h *= np.uint32(0x85EBCA6B)
+    h ^= h >> np.uint32(13)
+    h *= np.uint32(0xC2B2AE35)
+    h ^= h >> np.uint32(16)
+    return h
+
+
+def _keys_sharing_two_lds_groups(slots, want=16):
+    """int32 keys whose two LDS groups (lds_table.hpp as hashagg.hip's HaLt fills it in: g1 from
+    fmix32(key), g2 from fmix32 of that hash xor 0x9e3779b9, `slots` / 4 groups) both fall in
+    groups {0, 1}: they share 8 slots."""
+    found = []
+    for lo in range(0, 1 << 26, 1 << 22):
+        k = np.arange(lo, lo + (1 << 22), dtype=np.uint32)
+        h = _fmix32(k)
+        g1 = (h & np.uint32(slots - 1)) >> np.uint32(2)
+        g2 = (_fmix32(h ^ np.uint32(0x9E3779B9)) & np.uint32(slots - 1)) >> np.uint32(2)
+        found.extend(k[(g1 < 2) & (g2 < 2)].tolist())
+        if len(found) >= want:
+            break
+    return np.array(found[:want], dtype=np.int32)
+
+
+@pytest.mark.parametrize("table", ["narrow", "wide"])
+def test_both_lds_groups_full_spills_to_hbm(table):
+    """Keys that share the 8 slots of two LDS groups: every key past the eighth finds both of
+    its groups full and its rows aggregate straight into the HBM table (the insert loop's
+    last branch), here in the direct mode with one workgroup.  Narrow table: int32 key, one
+    float64 sum, no count(v); wide: count(v) asked for."""
+    slots = 8192 if table == "narrow" else 4096
+    crowd = _keys_sharing_two_lds_groups(slots)
+    assert len(crowd) >= 12
+    rng = np.random.default_rng(17)
+    n = 2000
+    pool = np.concatenate([crowd, np.arange(1 << 27, (1 << 27) + 100, dtype=np.int32)])
+    keys = pool[rng.integers(0, len(pool), n)]
+    keys[:len(crowd)] = crowd
+    v = rng.normal(size=n)
+    ha = _ha().HashAgg(keys.dtype, [v.dtype], nonnull=[table == "wide"])
+    ha.update(keys, [v])
+    gk, cnt, sums, nn = ha.finish()
+    uniq, inv = np.unique(keys, return_inverse=True)
+    np.testing.assert_array_equal(gk, uniq)
+    np.testing.assert_array_equal(cnt, np.bincount(inv, minlength=len(uniq)))
+    _, es, ec = oracle.groupby_reference(inv.astype(np.int64), v)
+    np.testing.assert_allclose(sums[0], es, rtol=1e-6, atol=1e-9)
+    if table == "wide":
+        np.testing.assert_array_equal(nn[0], ec)

@@ -130,3 +130,51 @@ def test_grouper_sort_on_device(dtype):
     got = [v for v in labels if v is not None]
     assert [(0 if v == v else 1, v if v == v else 0) for v in got] == [(0 if v == v else 1, v if v == v else 0) for v in exp]
     assert labels[-1] is None  # null last
+
+
+def _lds_hash32(k):
+    h = k.astype(np.uint32)
+    h ^= h >> np.uint32(16)
+    h *= np.uint32(0x85EBCA6B)
+    h ^= h >> np.uint32(13)
+    h *= np.uint32(0xC2B2AE35)
+    h ^= h >> np.uint32(16)
+    return h
+
+
+def test_both_lds_groups_full_spills_to_hbm():
+    """Key bits that share the 8 slots of two LDS groups (lds_table.hpp as hashset.hip's SiLt
+    fills it in for 4-byte keys: 2048 groups, g1 from the low bits of the murmur3-finalised
+    key bits, g2 from the top 11 bits of (hash xor 0x9e3779b9) * 0x2545f491): every key past
+    the eighth finds both groups full and goes straight to the HBM table (the insert loop's
+    last branch), here in the direct mode with one workgroup; with masked, NaN and unselected
+    rows among them."""
+    from vaex_amd import superutils
+    crowd = []
+    for lo in range(1 << 22, 1 << 26, 1 << 22):  # bits of small positive float32 numbers
+        k = np.arange(lo, lo + (1 << 22), dtype=np.uint32)
+        h = _lds_hash32(k)
+        g1 = (h & np.uint32(8191)) >> np.uint32(2)
+        g2 = ((h ^ np.uint32(0x9E3779B9)) * np.uint32(0x2545F491)) >> np.uint32(21)
+        crowd.extend(k[(g1 < 2) & (g2 < 2)].tolist())
+        if len(crowd) >= 16:
+            break
+    crowd = np.array(crowd[:16], dtype=np.uint32).view(np.float32)
+    assert len(crowd) >= 12
+    rng = np.random.default_rng(18)
+    n = 2000
+    pool = np.concatenate([crowd, np.arange(100, dtype=np.float32) + 0.5])
+    keys = pool[rng.integers(0, len(pool), n)]
+    keys[100:100 + len(crowd)] = crowd[::-1]
+    keys[rng.random(n) < 0.03] = np.nan
+    mask = rng.random(n) < 0.03
+    sel = rng.random(n) < 0.8
+    s = superutils.ordered_set_float32()
+    s.update(keys, mask, select=sel.astype(np.uint8))
+    ref = oracle.OrderedSet(nmaps=1)
+    ref.update(keys[sel], mask[sel])
+    # the keys in first-appearance order: every key's first row is the reference's
+    np.testing.assert_array_equal(s.key_array(), ref.key_array(np.float32))
+    assert len(s) == len(ref)
+    assert s.nan_count == int(np.isnan(keys[sel & ~mask]).sum()) and s.null_count == int((mask & sel).sum())
+    np.testing.assert_array_equal(s.map_ordinal(keys).astype(np.int64), ref.map_ordinal(keys).astype(np.int64))

@@ -248,6 +248,19 @@ inline unsigned blocks_for(uint64_t n, unsigned threads, unsigned per_cu = 8) {
     return (unsigned)b;
 }
 
+inline uint64_t next_pow2(uint64_t x) {
+    uint64_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+// resident workgroups of `kernel` per CU at this block size and dynamic LDS (at least 1)
+inline int blocks_per_cu(const void *kernel, int threads, size_t lds) {
+    int nb = 0;
+    VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds));
+    return nb > 1 ? nb : 1;
+}
+
 // upper bound on the rows one workgroup of a grid-stride kernel visits: launched with
 // `blocks` workgroups of `threads` lanes, each lane taking `unroll` rows per step (bounds
 // narrow per-workgroup partial sums; derive `blocks` from the launch's own dim3)

@@ -54,6 +54,7 @@
 
 #include "common.hpp"
 #include "hashset.hpp"
+#include "lds_table.hpp"
 
 using namespace vh;
 
@@ -89,7 +90,6 @@ constexpr uint64_t CT_DEFAULT_CAP = uint64_t(1) << 16;
 constexpr uint64_t CT_SAMPLE_MIN = uint64_t(1) << 20;
 constexpr uint64_t CT_SAMPLE_ROWS = uint64_t(1) << 16;
 
-template <typename T> using ct_kb_t = std::conditional_t<sizeof(T) == 8, uint64_t, uint32_t>;
 // 8-byte keys: one 1024-lane workgroup per CU (96 KiB of LDS); else two of 512 (64 KiB each)
 template <typename KB> constexpr int ct_threads() { return sizeof(KB) == 8 ? 1024 : 512; }
 template <typename KB> constexpr size_t ct_lds_bytes() { return (sizeof(KB) + 4) * (size_t)CT_LT; }
@@ -109,38 +109,8 @@ struct CtParams {
 // (key, count) into the HBM table: CAS on the key, one 64-bit add of the count.  New keys are
 // counted per workgroup in LDS (`wg_new`).  A probe sequence past max_probe raises overflow.
 __device__ inline void ct_insert(const CtDev &g, uint64_t kb, uint64_t cnt, uint32_t *wg_new) {
-    uint64_t pos = hash64(kb) & g.cap_mask;
-    for (uint64_t p = 0; p <= g.max_probe; p++) {
-        const uint64_t k = __hip_atomic_load(&g.tab[2 * pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool mine = k == kb;
-        if (!mine && k == SET_EMPTY) {
-            const uint64_t old = atomicCAS((unsigned long long *)&g.tab[2 * pos], (unsigned long long)SET_EMPTY,
-                                           (unsigned long long)kb);
-            if (old == SET_EMPTY) atomicAdd(wg_new, 1u);
-            mine = old == SET_EMPTY || old == kb;
-        }
-        if (mine) {
-            atomicAdd((unsigned long long *)&g.tab[2 * pos + 1], (unsigned long long)cnt);
-            return;
-        }
-        pos = (pos + 1) & g.cap_mask;
-    }
-    atomicOr((unsigned long long *)&g.ctr[K_OVERFLOW], 1ULL);
-}
-
-__device__ inline uint32_t ct_lds_hash(uint64_t kb) {  // murmur3 fmix32, as hashset.hip's LDS hash
-    uint32_t h = (uint32_t)kb ^ (uint32_t)(kb >> 32) * 0x9e3779b9u;
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ inline uint32_t ct_cas(uint32_t *p, uint32_t cmp, uint32_t val) { return atomicCAS(p, cmp, val); }
-__device__ inline uint64_t ct_cas(uint64_t *p, uint64_t cmp, uint64_t val) {
-    return atomicCAS(reinterpret_cast<unsigned long long *>(p), (unsigned long long)cmp, (unsigned long long)val);
+    set_claim(g.tab, g.cap_mask, g.max_probe, kb, wg_new, &g.ctr[K_OVERFLOW],
+              [&](uint64_t *count) { atomicAdd((unsigned long long *)count, (unsigned long long)cnt); });
 }
 
 // 8 consecutive rows of a column into registers (binning.hip load_rows8): wide loads when the
@@ -175,11 +145,11 @@ template <typename KB> struct CtLds {
 // `run` occurrences of a regular key into the LDS table, or straight to HBM when no slot
 template <typename KB> __device__ inline void ct_lds_add(const CtLds<KB> &t, const CtDev &g, KB k, uint32_t run) {
     constexpr KB EMPTY = ~KB(0);
-    uint32_t h = ct_lds_hash((uint64_t)k) & (CT_LT - 1);
+    uint32_t h = lds_hash((uint64_t)k) & (CT_LT - 1);
     for (int pr = 0; pr < CT_LDS_PROBES; pr++) {
         KB cur = t.keys[h];
         if (cur == EMPTY) {
-            cur = ct_cas(&t.keys[h], EMPTY, k);
+            cur = lds_cas(&t.keys[h], EMPTY, k);
             if (cur == EMPTY) {
                 atomicAdd(t.used, 1u);
                 cur = k;
@@ -195,8 +165,8 @@ template <typename KB> __device__ inline void ct_lds_add(const CtLds<KB> &t, con
 }
 
 template <typename T>
-__global__ __launch_bounds__(ct_threads<ct_kb_t<T>>()) void k_ct_count(CtParams p, CtDev g) {
-    using KB = ct_kb_t<T>;
+__global__ __launch_bounds__(ct_threads<kb_t<T>>()) void k_ct_count(CtParams p, CtDev g) {
+    using KB = kb_t<T>;
     constexpr int THREADS = ct_threads<KB>();
     constexpr KB EMPTY = ~KB(0);
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -371,28 +341,6 @@ __global__ __launch_bounds__(256) void k_ct_clear(uint64_t *tab, uint64_t cap) {
         reinterpret_cast<ulonglong2 *>(tab)[i] = make_ulonglong2(SET_EMPTY, 0);
 }
 
-// distinct keys of the sample and how many were seen once / twice (Chao1 inputs)
-__global__ __launch_bounds__(256) void k_ct_sample_stats(const uint64_t *tab, uint64_t cap, uint64_t *ctr) {
-    uint32_t d = 0, f1 = 0, f2 = 0;
-    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * 256) {
-        const ulonglong2 e = reinterpret_cast<const ulonglong2 *>(tab)[i];
-        if (e.x == SET_EMPTY) continue;
-        d++;
-        f1 += e.y == 1;
-        f2 += e.y == 2;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        d += __shfl_down(d, off, 64);
-        f1 += __shfl_down(f1, off, 64);
-        f2 += __shfl_down(f2, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0 && d) {
-        atomicAdd((unsigned long long *)&ctr[K_D], (unsigned long long)d);
-        if (f1) atomicAdd((unsigned long long *)&ctr[K_F1], (unsigned long long)f1);
-        if (f2) atomicAdd((unsigned long long *)&ctr[K_F2], (unsigned long long)f2);
-    }
-}
-
 // ---- finish ---------------------------------------------------------------------------------
 // key bits (zero-extended) <-> a u64 whose unsigned order is the key's numeric order; floats
 // by their bit pattern, so -0.0 sorts just before 0.0
@@ -482,12 +430,6 @@ __global__ __launch_bounds__(256) void k_ct_emit(const uint64_t *okey, const uin
 }
 
 // ---- host -------------------------------------------------------------------------------------
-static uint64_t ct_next_pow2(uint64_t x) {
-    uint64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
 static void ct_clear(CtTable &t) {
     if (t.clean || !t.cap) return;
     hipLaunchKernelGGL(k_ct_clear, dim3(blocks_for(t.cap, 256)), dim3(256), 0, stream(), t.buf.as<uint64_t>(), t.cap);
@@ -596,8 +538,9 @@ static uint64_t ct_size_from_sample(vh_counter *c, const T *keys, const uint8_t 
     S.clean = false;
     hipLaunchKernelGGL(k_ct_sample<T>, dim3(blocks_for(CT_SAMPLE_ROWS, 256)), dim3(256), 0, stream(), keys, mask, select, n,
                        CT_SAMPLE_ROWS, ct_dev(c, S, true));
-    hipLaunchKernelGGL(k_ct_sample_stats, dim3(blocks_for(S.cap, 256)), dim3(256), 0, stream(), S.buf.as<uint64_t>(), S.cap,
-                       c->ctr.as<uint64_t>());
+    static_assert(K_F1 == K_D + 1 && K_F2 == K_D + 2, "k_sample_stats adds to three consecutive counters");
+    hipLaunchKernelGGL(k_sample_stats<SampleSlotCounts>, dim3(blocks_for(S.cap, 256)), dim3(256), 0, stream(),
+                       SampleSlotCounts{S.buf.as<uint64_t>()}, S.cap, c->ctr.as<unsigned long long>() + K_D);
     VH_HIP(hipGetLastError());
     const auto k = ct_read_ctr(c);
     const double d = (double)k[K_D], f1 = (double)k[K_F1], f2 = (double)k[K_F2];
@@ -605,13 +548,13 @@ static uint64_t ct_size_from_sample(vh_counter *c, const T *keys, const uint8_t 
     double est = f2 > 0 ? d + f1 * f1 / (2 * f2) : (f1 > 0 ? (double)n : d);
     est = std::min(est, (double)n);
     // under 1/2 of the 3/4 limit, and not past 2^28 slots (4 GiB): a larger table is grown into
-    cap = std::max(cap, std::min<uint64_t>(ct_next_pow2((uint64_t)(est * 3) + 1), uint64_t(1) << 28));
+    cap = std::max(cap, std::min<uint64_t>(next_pow2((uint64_t)(est * 3) + 1), uint64_t(1) << 28));
     return cap;
 }
 
 template <typename T>
 static void ct_count_chunk(vh_counter *c, const void *keys, const uint8_t *mask, const uint8_t *select, uint64_t n) {
-    using KB = ct_kb_t<T>;
+    using KB = kb_t<T>;
     constexpr int THREADS = ct_threads<KB>();
     constexpr uint64_t STEP = (uint64_t)THREADS * CT_RPT;
     constexpr size_t lds = ct_lds_bytes<KB>();

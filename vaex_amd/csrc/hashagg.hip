@@ -55,6 +55,7 @@
 #include "engine.hpp"
 #include "common.hpp"
 #include "hashset.hpp"
+#include "lds_table.hpp"
 
 namespace vh {
 
@@ -79,20 +80,9 @@ constexpr int HA_SAMPLE_BLOCKS = 256;
 constexpr uint32_t HA_DEST_OVERFLOW = 0x80000000u;
 constexpr int HA_MAX_PROBE = 1 << 14;
 
-__host__ __device__ inline uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
 // 32-bit hash of the key bits: its top bits pick the bucket, its low bits the LDS group
 __device__ inline uint32_t ha_h(uint32_t kb) { return fmix32(kb); }
 __device__ inline uint32_t ha_h(uint64_t kb) { return (uint32_t)(hash64(kb) >> 32); }
-
-template <typename K> using kb_t = std::conditional_t<sizeof(K) == 8, uint64_t, uint32_t>;
 
 // key bits: <= 4-byte keys as int32 (signed, sign-extended) / uint32; 8-byte keys verbatim
 template <typename K> __device__ inline kb_t<K> ha_kb(K v) {
@@ -100,9 +90,6 @@ template <typename K> __device__ inline kb_t<K> ha_kb(K v) {
     else if constexpr (std::is_signed_v<K>) return (uint32_t)(int32_t)v;
     else return (uint32_t)v;
 }
-
-template <typename KB> __host__ __device__ constexpr KB kb_empty() { return ~KB(0); }
-template <typename KB> __host__ __device__ constexpr KB kb_closed() { return ~KB(0) - 1; }
 
 // a value as the 8 bytes pass A carries: float -> double bits, signed -> int64,
 // unsigned / bool -> uint64 (the AggSum upcast, superagg.cpp:289-346)
@@ -271,107 +258,23 @@ __device__ inline void lt_bump(const LdsTable<KB> &t, const HaTable &g, uint32_t
     else atomicAdd(&t.cn[slot], c);
 }
 
-// four consecutive key slots: one ds_read_b128 (4-byte keys) or two (8-byte keys)
-template <typename KB> struct alignas(16) KB4 {
-    KB v[4];
+// hashagg's two-choice table (lds_table.hpp): wide (N = false) or narrow, NV value columns.
+// g1 from the low bits of the key's bucket hash, g2 from a second mix of it; a row's payload
+// is its NV value bits
+template <typename KB_, int NV, bool N> struct HaLt {
+    using KB = KB_;
+    static constexpr uint32_t SLOTS = lt_slots<N>();
+    const LdsTable<KB> &t;
+    const HaTable &g;
+    __device__ KB *keys() const { return t.keys; }
+    __device__ void groups(KB kb, uint32_t &g1, uint32_t &g2) const {
+        const uint32_t h = ha_h(kb);
+        g1 = (h & (SLOTS - 1)) >> 2;
+        g2 = (fmix32(h ^ 0x9e3779b9u) & (SLOTS - 1)) >> 2;
+    }
+    __device__ void hit(uint32_t slot, const uint64_t *vb) const { lt_bump<KB, NV, N>(t, g, slot, vb); }
+    __device__ void spill(KB kb, const uint64_t *vb) const { ha_global_row<NV>(g, (uint64_t)kb, vb); }
 };
-
-__device__ inline uint32_t lt_cas(uint32_t *p, uint32_t cmp, uint32_t val) { return atomicCAS(p, cmp, val); }
-__device__ inline uint64_t lt_cas(uint64_t *p, uint64_t cmp, uint64_t val) {
-    return atomicCAS(reinterpret_cast<unsigned long long *>(p), (unsigned long long)cmp, (unsigned long long)val);
-}
-
-// Two-choice LDS table: a key lives in one of two 4-slot groups (g1 from its hash, g2 from a
-// second mix of it), so a lookup reads both groups at once and almost never needs more:
-// with ~2300 keys in 1024 groups the less loaded of two groups is rarely full (one-group
-// linear probing displaced ~5 % of keys, and the lanes holding them serialised every wave:
-// 4.6 of pass B's 7.3 ms, VH_HA_DEBUG ablation).  Insertion CASes the first EMPTY slot of
-// the group with more room; two lanes inserting one new key at once may place it in both
-// groups -- harmless, both records merge into the same HBM slot.  A key whose two groups are
-// full aggregates straight into the HBM table.  Keys whose bits are EMPTY / CLOSED live in
-// the two side records.
-template <typename KB, bool N> __device__ inline void lt2_groups(KB kb, uint32_t &g1, uint32_t &g2) {
-    constexpr uint32_t S = lt_slots<N>();
-    const uint32_t h = ha_h(kb);
-    g1 = (h & (S - 1)) >> 2;
-    g2 = (fmix32(h ^ 0x9e3779b9u) & (S - 1)) >> 2;
-}
-
-template <typename KB> __device__ inline uint32_t lt2_find(const KB4<KB> &q1, const KB4<KB> &q2, uint32_t g1, uint32_t g2,
-                                                         KB kb) {
-    uint32_t slot = ~0u;
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-        if (q2.v[j] == kb) slot = 4 * g2 + j;
-        if (q1.v[j] == kb) slot = 4 * g1 + j;
-    }
-    return slot;
-}
-
-// a key not found in either group: insert it (or find it, if another lane just did)
-template <typename KB, int NV, bool N>
-__device__ inline void lt2_insert(const LdsTable<KB> &t, const HaTable &g, KB kb, const uint64_t *vb) {
-    constexpr KB EMPTY = kb_empty<KB>();
-    uint32_t g1, g2;
-    lt2_groups<KB, N>(kb, g1, g2);
-    for (int it = 0; it < 64; it++) {
-        const KB4<KB> q1 = *reinterpret_cast<const KB4<KB> *>(t.keys + 4 * g1);
-        const KB4<KB> q2 = *reinterpret_cast<const KB4<KB> *>(t.keys + 4 * g2);
-        const uint32_t hit = lt2_find(q1, q2, g1, g2, kb);
-        if (hit != ~0u) {
-            lt_bump<KB, NV, N>(t, g, hit, vb);
-            return;
-        }
-        int e1 = 0, e2 = 0, f1 = -1, f2 = -1;
-#pragma unroll
-        for (int j = 3; j >= 0; j--) {
-            if (q1.v[j] == EMPTY) {
-                e1++;
-                f1 = j;
-            }
-            if (q2.v[j] == EMPTY) {
-                e2++;
-                f2 = j;
-            }
-        }
-        if (e1 == 0 && e2 == 0) break;
-        const uint32_t pos = e1 >= e2 ? 4 * g1 + f1 : 4 * g2 + f2;
-        const KB cur = lt_cas(&t.keys[pos], EMPTY, kb);
-        if (cur == EMPTY || cur == kb) {
-            lt_bump<KB, NV, N>(t, g, pos, vb);
-            return;
-        }
-        // another key took the slot: read the groups again
-    }
-    ha_global_row<NV>(g, (uint64_t)kb, vb);
-}
-
-// M entries at once: both group reads of every entry are issued together and the hits
-// aggregated with fire-and-forget LDS atomics; only keys new to the table take lt2_insert.
-template <typename KB, int NV, int M, bool N>
-__device__ inline void lt2_add_many(const LdsTable<KB> &t, const HaTable &g, const KB *kb,
-                                    const uint64_t (*vb)[NV > 0 ? NV : 1], const bool *valid) {
-    constexpr uint32_t S = lt_slots<N>();
-    KB4<KB> q1[M], q2[M];
-    uint32_t g1[M], g2[M];
-#pragma unroll
-    for (int i = 0; i < M; i++) {
-        lt2_groups<KB, N>(kb[i], g1[i], g2[i]);
-        q1[i] = *reinterpret_cast<const KB4<KB> *>(t.keys + 4 * g1[i]);
-        q2[i] = *reinterpret_cast<const KB4<KB> *>(t.keys + 4 * g2[i]);
-    }
-    bool slow[M];
-#pragma unroll
-    for (int i = 0; i < M; i++) {
-        uint32_t slot = lt2_find(q1[i], q2[i], g1[i], g2[i], kb[i]);
-        if (kb[i] >= kb_closed<KB>()) slot = S + (uint32_t)(kb[i] - kb_closed<KB>());
-        slow[i] = valid[i] && slot == ~0u;
-        if (valid[i] && slot != ~0u) lt_bump<KB, NV, N>(t, g, slot, vb[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < M; i++)
-        if (slow[i]) lt2_insert<KB, NV, N>(t, g, kb[i], vb[i]);
-}
 
 // merge the LDS table into the HBM table (after a workgroup barrier, every thread); the
 // workgroup's new keys are added to g.used once
@@ -423,16 +326,6 @@ struct HaParams {
     uint64_t dummy0;       // first dummy slot (idle lanes of the stream-out write there)
 };
 
-struct HaUnit {
-    uint32_t bucket, w_begin, w_end, pad;
-};
-
-__device__ inline void ha_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 // ---- sample -------------------------------------------------------------------------------
 template <typename K>
 __global__ __launch_bounds__(HA_THREADS) void k_ha_sample(const K *keys, uint64_t n, uint64_t block_stride,
@@ -456,51 +349,13 @@ __global__ __launch_bounds__(HA_THREADS) void k_ha_sample(const K *keys, uint64_
         atomicAdd(&h[ha_h(kb) >> (32 - HA_FINE_LOG2)], 1u);
         const uint64_t key = (uint64_t)kb;
         if (key == SET_EMPTY) continue;  // the estimate can miss one key
-        uint64_t pos = hash64(key) & smask;
-        for (int p = 0; p < HA_MAX_PROBE; p++) {
-            uint64_t cur = __hip_atomic_load(&skeys[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == SET_EMPTY)
-                cur = atomicCAS((unsigned long long *)&skeys[pos], (unsigned long long)SET_EMPTY, (unsigned long long)key);
-            if (cur == SET_EMPTY || cur == key) {
-                atomicAdd(&scnt[pos], 1u);
-                break;
-            }
-            pos = (pos + 1) & smask;
-        }
+        sample_insert(skeys, scnt, smask, key);
     }
     for (int off = 32; off > 0; off >>= 1) adj += __shfl_down(adj, off, 64);
     if ((threadIdx.x & 63) == 0 && adj) atomicAdd(&fine_hist[(1u << HA_FINE_LOG2) + 3], (unsigned long long)adj);
     __syncthreads();
     for (uint32_t t = threadIdx.x; t < (1u << HA_FINE_LOG2); t += HA_THREADS)
         if (h[t]) atomicAdd(&fine_hist[t], (unsigned long long)h[t]);
-}
-
-// distinct keys of the sample, and how many were seen once / twice (Chao1 inputs)
-__global__ __launch_bounds__(256) void k_ha_sample_stats(const uint32_t *scnt, uint64_t slots,
-                                                         unsigned long long *stats) {
-    __shared__ uint32_t part[3][4];
-    uint32_t d = 0, f1 = 0, f2 = 0;
-    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * 256) {
-        const uint32_t c = scnt[i];
-        d += c != 0;
-        f1 += c == 1;
-        f2 += c == 2;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        d += __shfl_down(d, off, 64);
-        f1 += __shfl_down(f1, off, 64);
-        f2 += __shfl_down(f2, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {  // one atomic per block and counter, not per wave
-        part[0][threadIdx.x >> 6] = d;
-        part[1][threadIdx.x >> 6] = f1;
-        part[2][threadIdx.x >> 6] = f2;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const uint32_t v = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
-        if (v) atomicAdd(&stats[threadIdx.x], (unsigned long long)v);
-    }
 }
 
 // ---- pass A -------------------------------------------------------------------------------
@@ -550,7 +405,7 @@ __device__ inline void ha_commit(const HaScatterLds<KB> &l, const HaParams &hp, 
     __shared__ uint32_t s_total, s_over;
     const uint32_t P = hp.P;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    ha_lds_barrier();
+    lds_barrier();
     {
         const uint32_t per = (P + HA_THREADS - 1) / HA_THREADS;
         const uint32_t t0 = threadIdx.x * per;
@@ -562,7 +417,7 @@ __device__ inline void ha_commit(const HaScatterLds<KB> &l, const HaParams &hp, 
             if (lane >= off) inc += y;
         }
         if (lane == 63) l.wave_sums[wave] = inc;
-        ha_lds_barrier();
+        lds_barrier();
         uint32_t wave_base = 0, total = 0;
         for (int k = 0; k < HA_THREADS / 64; k++) {
             if (k < wave) wave_base += l.wave_sums[k];
@@ -578,7 +433,7 @@ __device__ inline void ha_commit(const HaScatterLds<KB> &l, const HaParams &hp, 
             s_over = 0;
         }
     }
-    ha_lds_barrier();
+    lds_barrier();
     bool over = false;
 #pragma unroll
     for (int r = 0; r < HA_RPT; r++) {
@@ -594,7 +449,7 @@ __device__ inline void ha_commit(const HaScatterLds<KB> &l, const HaParams &hp, 
         for (int v = 0; v < NV; v++) l.sv[v * (HA_BATCH + 1) + pos] = vb[r][v];
     }
     if (over) s_over = 1;
-    ha_lds_barrier();
+    lds_barrier();
     const uint32_t tot = s_total;
     const uint64_t dummy = hp.dummy0 + (uint64_t)blockIdx.x * HA_THREADS + threadIdx.x;
 #pragma unroll
@@ -626,12 +481,12 @@ __device__ inline void ha_commit(const HaScatterLds<KB> &l, const HaParams &hp, 
         }
         if (novf) atomicAdd(&d_ha_overflow_rows, (unsigned long long)novf);
     }
-    ha_lds_barrier();
+    lds_barrier();
     for (uint32_t t = threadIdx.x; t < P; t += HA_THREADS) {
         l.base[t] += l.hist[t];
         l.hist[t] = 0;
     }
-    ha_lds_barrier();
+    lds_barrier();
 }
 
 // top p_log2 bits of the key hash (branch-free: p_log2 = 0 gives bucket 0)
@@ -955,7 +810,7 @@ __global__ __launch_bounds__(HA_THREADS) void k_ha_scatter_k4(HaParams hp, HaTab
             for (int r = 0; r < SB * HA_RPT; r++) took = took || rank[r] >= 0;
             if (!__syncthreads_or(took)) continue;
         } else {
-            ha_lds_barrier();
+            lds_barrier();
         }
         if (threadIdx.x < 64) {
             const uint32_t per = (P + 63) / 64;
@@ -981,7 +836,7 @@ __global__ __launch_bounds__(HA_THREADS) void k_ha_scatter_k4(HaParams hp, HaTab
             if (lane == 63) wave_sums[0] = inc;
         }
         // B2: rows stage their key bits and values at their sorted positions
-        ha_lds_barrier();
+        lds_barrier();
         const uint32_t tot = wave_sums[0];
 #pragma unroll
         for (int r = 0; r < SB * HA_RPT; r++) {
@@ -992,7 +847,7 @@ __global__ __launch_bounds__(HA_THREADS) void k_ha_scatter_k4(HaParams hp, HaTab
         }
         // B3: the sorted runs stream to the regions; a full region (sampling miss) sends
         // its rows to the HBM table
-        ha_lds_barrier();
+        lds_barrier();
         for (uint32_t k = threadIdx.x; k < tot; k += HA_THREADS) {
             const uint32_t key = sk[k];
             const uint32_t t = ha_bucket(hp, key);
@@ -1010,7 +865,7 @@ __global__ __launch_bounds__(HA_THREADS) void k_ha_scatter_k4(HaParams hp, HaTab
         }
     }
     if (novf) atomicAdd(&d_ha_overflow_rows, (unsigned long long)novf);
-    ha_lds_barrier();
+    lds_barrier();
     for (uint32_t t = threadIdx.x; t < P; t += HA_THREADS) hp.fills[(uint64_t)t * hp.W + w] = base[t] - (uint32_t)hp.toff[t];
     if (RUNS && threadIdx.x == 0 && s_new && atomicAdd(g.used, s_new) + s_new > g.max_used) atomicOr(g.err, 1u);
 }
@@ -1032,11 +887,11 @@ __global__ __launch_bounds__(64) void k_ha_tail(HaParams hp, HaTable g, uint64_t
 // lane per load: consecutive lanes read consecutive entries (a wave's load is contiguous
 // unless it crosses a region end); a lane finds the region of its entry by a forward scan.
 template <typename KB, int NV, bool N>
-__global__ __launch_bounds__(HB_THREADS) void k_ha_reduce(HaParams hp, HaTable g, const HaUnit *units) {
+__global__ __launch_bounds__(HB_THREADS) void k_ha_reduce(HaParams hp, HaTable g, const HashUnit *units) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     __shared__ uint32_t s_fill[1024];
     __shared__ uint32_t s_pre[1025];
-    const HaUnit u = units[blockIdx.x];
+    const HashUnit u = units[blockIdx.x];
     const uint32_t b = u.bucket;
     const uint32_t cap = hp.cap[b];
     const uint32_t nw = u.w_end - u.w_begin;  // <= 1024 (host checks)
@@ -1102,7 +957,7 @@ __global__ __launch_bounds__(HB_THREADS) void k_ha_reduce(HaParams hp, HaTable g
         } else {
             constexpr int MM = sizeof(KB) == 4 ? HB_M / 2 : HB_M / 4;  // 128 VGPRs at 1024 threads
 #pragma unroll
-            for (int h0 = 0; h0 < HB_M; h0 += MM) lt2_add_many<KB, NV, MM, N>(t, g, B.kb + h0, B.vb + h0, B.valid + h0);
+            for (int h0 = 0; h0 < HB_M; h0 += MM) lt2_add_many<MM>(HaLt<KB, NV, N>{t, g}, B.kb + h0, B.vb + h0, B.valid + h0);
         }
     };
     constexpr uint32_t STEP = HB_THREADS * HB_M;
@@ -1154,7 +1009,7 @@ template <typename KB> __device__ inline uint32_t ha_sub(KB kb, uint32_t p_log2,
 }
 
 template <typename KB, int NV>
-__global__ __launch_bounds__(HB_THREADS) void k_ha_repart(HaParams hp, HaTable g, const HaUnit *units, RepartParams rq) {
+__global__ __launch_bounds__(HB_THREADS) void k_ha_repart(HaParams hp, HaTable g, const HashUnit *units, RepartParams rq) {
     __shared__ uint32_t s_fill[1024];
     __shared__ uint32_t s_pre[1025];
     __shared__ uint32_t hist[HR_MAX_S], boff[HR_MAX_S], dbase[HR_MAX_S], cursor[HR_MAX_S], s_tot;
@@ -1162,7 +1017,7 @@ __global__ __launch_bounds__(HB_THREADS) void k_ha_repart(HaParams hp, HaTable g
     __shared__ uint64_t svb[NV > 0 ? NV : 1][HR_CH];
     __shared__ uint8_t ssub[HR_CH];
     const uint32_t ui = blockIdx.x;
-    const HaUnit u = units[ui];
+    const HashUnit u = units[ui];
     const uint32_t b = u.bucket, S = rq.S;
     const uint32_t cap = hp.cap[b];
     const uint32_t nw = u.w_end - u.w_begin;
@@ -1299,7 +1154,7 @@ __global__ __launch_bounds__(HB_THREADS) void k_ha_direct(HaParams hp, HaTable g
                 for (int v = 0; v < NV; v++) vb[r][v] = ha_load_val(hp.vals[v], hp.vdtype[v], i);
             }
         }
-        lt2_add_many<KB, NV, U, N>(t, g, kb, vb, valid);
+        lt2_add_many<U>(HaLt<KB, NV, N>{t, g}, kb, vb, valid);
     }
     __syncthreads();
     lt_merge<KB, NV, N>(t, g, HB_THREADS);
@@ -1767,12 +1622,6 @@ template <typename F> static void dispatch_kb(int key_dtype, F &&f) {
     else f(uint32_t());
 }
 
-static uint64_t next_pow2(uint64_t x) {
-    uint64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
 // grow (rehash) the HBM table to hold `need` keys at <= 1/2 load
 static void ensure_table(vh_hashagg *h, uint64_t need) {
     const uint64_t want = std::max<uint64_t>(1u << 16, next_pow2(2 * need));
@@ -1812,53 +1661,37 @@ static uint32_t read_used(vh_hashagg *h, uint32_t *err) {
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-static int blocks_per_cu(const void *kernel, int threads, size_t lds) {
-    int nb = 0;
-    VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds));
-    return std::max(1, nb);
-}
-
 // one update over n <= 2^30 device-resident rows
 static void update_device(vh_hashagg *h, HaScratch &S, const void *keys, const void *const *vals, uint64_t n) {
     hipStream_t st = stream();
     const int nv = h->nv;
     const int kbs = key_bits_size(h->key_dtype);
     // ---- sample: fine bucket histogram + distinct estimate
-    const uint64_t sslots = 1ull << 21;
-    const uint64_t nbatch = (n + HA_BATCH - 1) / HA_BATCH;
-    const uint64_t sblocks = std::min<uint64_t>(nbatch, HA_SAMPLE_BLOCKS);
-    const uint64_t bstride = std::max<uint64_t>(HA_BATCH, n / sblocks);
-    const uint32_t FINE = 1u << HA_FINE_LOG2;
-    S.sample.ensure(sslots * 12 + 8 * FINE + 64);
-    uint64_t *skeys = S.sample.as<uint64_t>();
-    uint32_t *scnt = reinterpret_cast<uint32_t *>(skeys + sslots);
-    unsigned long long *fine = reinterpret_cast<unsigned long long *>(scnt + sslots);
-    unsigned long long *stats = fine + FINE;
-    VH_HIP(hipMemsetAsync(skeys, 0xff, 8 * sslots, st));
-    VH_HIP(hipMemsetAsync(scnt, 0, 4 * sslots + 8 * FINE + 64, st));
+    static_assert(HA_BATCH == HP_BATCH && HA_FINE_LOG2 == HP_FINE_LOG2 && HA_DEST_OVERFLOW == HP_DEST_OVER, "hash_plan.hpp");
+    const uint64_t sslots = HP_SAMPLE_SLOTS;
+    const uint32_t FINE = HP_FINE;
+    const HashSampleGeom sg = hash_sample_geom(n, HA_SAMPLE_BLOCKS);
+    const SampleBuf smp = sample_reset(S.sample, st);
     {
         TimedScope ts("ha_sample");
         VH_DISPATCH_KEY(h->key_dtype, K,
-                        hipLaunchKernelGGL(k_ha_sample<K>, dim3(sblocks), dim3(HA_THREADS), 0, st,
-                                           static_cast<const K *>(keys), n, bstride, fine, skeys, scnt, sslots - 1));
-        hipLaunchKernelGGL(k_ha_sample_stats, dim3(blocks_for(sslots, 256, 4)), dim3(256), 0, st, scnt, sslots, stats);
+                        hipLaunchKernelGGL(k_ha_sample<K>, dim3(sg.sblocks), dim3(HA_THREADS), 0, st,
+                                           static_cast<const K *>(keys), n, sg.bstride, smp.fine, smp.skeys, smp.scnt, sslots - 1));
+        hipLaunchKernelGGL(k_sample_stats<SampleCounts>, dim3(blocks_for(sslots, 256, 4)), dim3(256), 0, st,
+                           SampleCounts{smp.scnt}, sslots, smp.stats);
         VH_HIP(hipGetLastError());
     }
     thread_local PinnedBuf fb;  // page-locked sample read-back
     fb.ensure(8 * (FINE + 4));
     const uint64_t *fh = fb.as<uint64_t>();
-    VH_HIP(hipMemcpyAsync(fb.ptr, fine, 8 * (FINE + 4), hipMemcpyDeviceToHost, st));
+    VH_HIP(hipMemcpyAsync(fb.ptr, smp.fine, 8 * (FINE + 4), hipMemcpyDeviceToHost, st));
     VH_HIP(hipStreamSynchronize(st));
-    uint64_t sampled = 0;
-    for (uint32_t i = 0; i < FINE; i++) sampled += fh[i];
-    const double ds = (double)fh[FINE], f1 = (double)fh[FINE + 1], f2 = (double)fh[FINE + 2];
+    const uint64_t sampled = hash_sampled_rows(fh);
     // clustered keys: most sampled rows equal their next row (a sorted key column)
     bool runs = sampled > 0 && (double)fh[FINE + 3] > 0.5 * (double)sampled;
     if (const char *e = getenv("VH_HA_RUNS")) runs = atoi(e) != 0;  // A/B: same results either way
-    double dest;
-    if (sampled >= n) dest = ds;  // every row sampled: exact
-    else dest = f2 > 0 ? ds + f1 * f1 / (2 * f2) : ds + f1 * (f1 - 1) / 2;  // Chao1
-    dest = std::min<double>(dest, (double)n);
+    const double dest = hash_estimate_keys(sampled, (double)fh[FINE], (double)fh[FINE + 1], (double)fh[FINE + 2], n,
+                                           /*whole_chunk=*/false, /*at_least_one=*/false);
     uint32_t used_before = h->slots ? read_used(h, nullptr) : 0;
     ensure_table(h, (uint64_t)dest + used_before);
     HaTable g = table_view(h->tab.ptr, h->slots, nv, h->vfloat, h->nnmask);
@@ -1873,8 +1706,7 @@ static void update_device(vh_hashagg *h, HaScratch &S, const void *keys, const v
     }();
     const bool narrow = narrow_on && kbs == 4 && nv <= 1 && h->nnmask == 0;
     const double target_keys = narrow ? lt_target_keys<true>() : lt_target_keys<false>();
-    uint32_t p_log2 = 0;
-    while (p_log2 < HA_MAX_P_LOG2 && dest / (double)(1u << p_log2) > target_keys) p_log2++;
+    const uint32_t p_log2 = hash_p_log2(dest, target_keys, HA_MAX_P_LOG2);
 
     HaParams hp{};
     hp.keys = keys;
@@ -1905,17 +1737,15 @@ static void update_device(vh_hashagg *h, HaScratch &S, const void *keys, const v
             }));
         };
         with_direct([&](auto kernel) { bpc = blocks_per_cu(reinterpret_cast<const void *>(kernel), HB_THREADS, lt_lds); });
-        const uint64_t W = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cu_count() * bpc,
-                                                                     (n + 4 * HB_THREADS - 1) / (4 * HB_THREADS)));
-        hp.rows_per_wg = (n + W - 1) / W;
+        const HashDirect d = hash_plan_direct(n, cu_count(), bpc, HB_THREADS);
+        hp.rows_per_wg = d.rows_per_wg;
         TimedScope ts("ha_direct");
-        with_direct([&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)W), dim3(HB_THREADS), lt_lds, st, hp, g); });
+        with_direct([&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)d.W), dim3(HB_THREADS), lt_lds, st, hp, g); });
         VH_HIP(hipGetLastError());
         return;
     }
     const uint32_t P = hp.P;
-    std::vector<uint64_t> bh(P, 0);
-    for (uint32_t i = 0; i < FINE; i++) bh[i >> (HA_FINE_LOG2 - p_log2)] += fh[i];
+    const std::vector<uint64_t> bh = hash_fold_fine(fh, p_log2);
 
     // ---- pass A geometry
     // the fast pass A: 4- or 8-byte keys, float64 values, 16-byte aligned columns; rows past
@@ -1977,22 +1807,11 @@ static void update_device(vh_hashagg *h, HaScratch &S, const void *keys, const v
             bpc = blocks_per_cu(reinterpret_cast<const void *>(k_ha_scatter<K, NV>), HA_THREADS, lds_a);
         }));
     }
-    bpc = std::min(bpc, 4);
-    const uint32_t W = std::min<uint32_t>(1024, (uint32_t)cu_count() * bpc);
-    // pass-A workgroup w takes batches w, w + W, ...: at most ceil(batches / W) of them
-    const uint64_t rows_per_wg = (nbatch + W - 1) / W * HA_BATCH;
-    std::vector<uint32_t> cap(P);
-    std::vector<uint64_t> toff(P);
-    uint64_t stride = 0;
-    for (uint32_t t = 0; t < P; t++) {
-        const double e = (double)rows_per_wg * (double)bh[t] / (double)std::max<uint64_t>(sampled, 1);
-        uint64_t c = (uint64_t)(e * 1.04 + 6.0 * std::sqrt(e + 1.0)) + 32;
-        c = std::min<uint64_t>((c + 7) & ~uint64_t(7), rows_per_wg + 8);
-        cap[t] = (uint32_t)c;
-        toff[t] = stride;
-        stride += c;
-    }
-    if (stride + rows_per_wg >= (uint64_t)HA_DEST_OVERFLOW) fail(VH_ERR_RUNTIME, "hashagg: region table too large");
+    HashPlan pl;
+    if (!hash_plan_partition(n, cu_count(), bpc, p_log2, bh, sampled, pl)) fail(VH_ERR_RUNTIME, "hashagg: region table too large");
+    const uint32_t W = pl.W;
+    const uint64_t stride = pl.stride;
+    const std::vector<HashUnit> &units = pl.units;
     const uint64_t total = stride * W + (uint64_t)W * HA_THREADS;  // regions + dummy slots
     if (nv == 1 && (kbs == 8 || VH_HA_PACK4)) {
         S.entries.ensure(16 * total + 64);  // packed {key, value} entries
@@ -2000,27 +1819,17 @@ static void update_device(vh_hashagg *h, HaScratch &S, const void *keys, const v
         S.entries.ensure((uint64_t)kbs * total + 16);
         if (nv) S.vbits.ensure(8 * total * nv + 32);
     }
-    // pass-B work units: buckets split over ranges of pass-A workgroups by expected size
-    std::vector<HaUnit> units;
-    const double target = std::max(1.0, (double)n / ((double)cu_count() * 2));
-    for (uint32_t t = 0; t < P; t++) {
-        const double e = (double)n * (double)bh[t] / (double)std::max<uint64_t>(sampled, 1);
-        const uint32_t gq = (uint32_t)std::min<double>(W, std::max(1.0, std::ceil(e / target)));
-        for (uint32_t k = 0; k < gq; k++)
-            units.push_back({t, (uint32_t)((uint64_t)W * k / gq), (uint32_t)((uint64_t)W * (k + 1) / gq), 0});
-    }
-    const uint64_t meta_bytes = 4 * (uint64_t)P + 8 * (uint64_t)P + 4 * (uint64_t)P * W + sizeof(HaUnit) * units.size() + 256;
-    S.meta.ensure(meta_bytes);
+    S.meta.ensure(pl.meta.bytes);
     unsigned char *mb = S.meta.as<unsigned char>();
-    uint64_t *d_toff = reinterpret_cast<uint64_t *>(mb);
-    HaUnit *d_units = reinterpret_cast<HaUnit *>(d_toff + P);
-    uint32_t *d_cap = reinterpret_cast<uint32_t *>(d_units + units.size());
-    uint32_t *d_fills = d_cap + P;
-    VH_HIP(hipMemcpyAsync(d_toff, toff.data(), 8 * (uint64_t)P, hipMemcpyHostToDevice, st));
-    VH_HIP(hipMemcpyAsync(d_units, units.data(), sizeof(HaUnit) * units.size(), hipMemcpyHostToDevice, st));
-    VH_HIP(hipMemcpyAsync(d_cap, cap.data(), 4 * (uint64_t)P, hipMemcpyHostToDevice, st));
+    uint64_t *d_toff = reinterpret_cast<uint64_t *>(mb + pl.meta.toff);
+    HashUnit *d_units = reinterpret_cast<HashUnit *>(mb + pl.meta.units);
+    uint32_t *d_cap = reinterpret_cast<uint32_t *>(mb + pl.meta.cap);
+    uint32_t *d_fills = reinterpret_cast<uint32_t *>(mb + pl.meta.fills);
+    VH_HIP(hipMemcpyAsync(d_toff, pl.toff.data(), 8 * (uint64_t)P, hipMemcpyHostToDevice, st));
+    VH_HIP(hipMemcpyAsync(d_units, units.data(), sizeof(HashUnit) * units.size(), hipMemcpyHostToDevice, st));
+    VH_HIP(hipMemcpyAsync(d_cap, pl.cap.data(), 4 * (uint64_t)P, hipMemcpyHostToDevice, st));
     hp.W = W;
-    hp.rows_per_wg = rows_per_wg;
+    hp.rows_per_wg = pl.rows_per_wg;
     hp.wg_stride = stride;
     hp.cap = d_cap;
     hp.toff = d_toff;
@@ -2079,60 +1888,35 @@ static void update_device(vh_hashagg *h, HaScratch &S, const void *keys, const v
         const char *e = getenv("VH_HA_REPART");
         return !e || atoi(e) != 0;
     }();
-    const double kpb = dest / (double)P;
     uint32_t S_sub = 1;
-    if (repart_on && p_log2 == HA_MAX_P_LOG2 && kpb > target_keys * 1.25)
-        S_sub = std::min<uint32_t>(HR_MAX_S, (uint32_t)std::ceil(kpb / target_keys));
+    if (repart_on) S_sub = hash_repart_subs(dest, p_log2, HA_MAX_P_LOG2, target_keys, HR_MAX_S);
     HaParams hpb = hp;
-    std::vector<HaUnit> units_b;
-    HaUnit *d_units_b = d_units;
+    HashRepart rp;
+    const std::vector<HashUnit> *units_b = &units;
+    HashUnit *d_units_b = d_units;
     if (S_sub > 1) {
+        hash_plan_repart(n, pl, bh, sampled, S_sub, rp);
         const uint32_t U = (uint32_t)units.size();
-        std::vector<uint64_t> rbase(U);
-        std::vector<uint32_t> rcap(U);
-        uint64_t total2 = 0;
-        for (uint32_t ui = 0; ui < U; ui++) {
-            const HaUnit &un = units[ui];
-            // the unit's entries: at most its regions' capacities; expected ~ n p_b * share
-            const double e = (double)n * (double)bh[un.bucket] / (double)std::max<uint64_t>(sampled, 1) *
-                             (double)(un.w_end - un.w_begin) / (double)W;
-            const double es = e / S_sub;
-            uint64_t c = (uint64_t)(es * 1.05 + 8.0 * std::sqrt(es + 1.0)) + 64;
-            c = (c + 7) & ~uint64_t(7);
-            rcap[ui] = (uint32_t)c;
-            rbase[ui] = total2;
-            total2 += c * S_sub;
-        }
+        const uint64_t total2 = rp.total, P2 = (uint64_t)U * S_sub;
         if (nv == 1 && (kbs == 8 || VH_HA_PACK4)) {
             S.entries2.ensure(16 * total2 + 64);
         } else {
             S.entries2.ensure((uint64_t)kbs * total2 + 16);
             if (nv) S.vbits2.ensure(8 * total2 * nv + 32);
         }
-        const uint64_t P2 = (uint64_t)U * S_sub;
-        units_b.resize(P2);
-        std::vector<uint64_t> toff2(P2);
-        std::vector<uint32_t> cap2(P2);
-        for (uint32_t ui = 0; ui < U; ui++)
-            for (uint32_t q = 0; q < S_sub; q++) {
-                const uint64_t gi = (uint64_t)ui * S_sub + q;
-                units_b[gi] = {(uint32_t)gi, 0, 1, 0};
-                toff2[gi] = rbase[ui] + (uint64_t)q * rcap[ui];
-                cap2[gi] = rcap[ui];
-            }
-        S.meta2.ensure(8 * (uint64_t)U + 4 * (uint64_t)U + 8 * P2 + 4 * P2 + 4 * P2 + sizeof(HaUnit) * P2 + 256);
+        S.meta2.ensure(rp.meta.bytes);
         unsigned char *m2 = S.meta2.as<unsigned char>();
-        uint64_t *d_rbase = reinterpret_cast<uint64_t *>(m2);
-        uint64_t *d_toff2 = d_rbase + U;
-        HaUnit *d_u2 = reinterpret_cast<HaUnit *>(d_toff2 + P2);
-        uint32_t *d_rcap = reinterpret_cast<uint32_t *>(d_u2 + P2);
-        uint32_t *d_cap2 = d_rcap + U;
-        uint32_t *d_fills2 = d_cap2 + P2;
-        VH_HIP(hipMemcpyAsync(d_rbase, rbase.data(), 8 * (uint64_t)U, hipMemcpyHostToDevice, st));
-        VH_HIP(hipMemcpyAsync(d_rcap, rcap.data(), 4 * (uint64_t)U, hipMemcpyHostToDevice, st));
-        VH_HIP(hipMemcpyAsync(d_toff2, toff2.data(), 8 * P2, hipMemcpyHostToDevice, st));
-        VH_HIP(hipMemcpyAsync(d_cap2, cap2.data(), 4 * P2, hipMemcpyHostToDevice, st));
-        VH_HIP(hipMemcpyAsync(d_u2, units_b.data(), sizeof(HaUnit) * P2, hipMemcpyHostToDevice, st));
+        uint64_t *d_rbase = reinterpret_cast<uint64_t *>(m2 + rp.meta.rbase);
+        uint64_t *d_toff2 = reinterpret_cast<uint64_t *>(m2 + rp.meta.toff2);
+        HashUnit *d_u2 = reinterpret_cast<HashUnit *>(m2 + rp.meta.units);
+        uint32_t *d_rcap = reinterpret_cast<uint32_t *>(m2 + rp.meta.rcap);
+        uint32_t *d_cap2 = reinterpret_cast<uint32_t *>(m2 + rp.meta.cap2);
+        uint32_t *d_fills2 = reinterpret_cast<uint32_t *>(m2 + rp.meta.fills2);
+        VH_HIP(hipMemcpyAsync(d_rbase, rp.rbase.data(), 8 * (uint64_t)U, hipMemcpyHostToDevice, st));
+        VH_HIP(hipMemcpyAsync(d_rcap, rp.rcap.data(), 4 * (uint64_t)U, hipMemcpyHostToDevice, st));
+        VH_HIP(hipMemcpyAsync(d_toff2, rp.toff2.data(), 8 * P2, hipMemcpyHostToDevice, st));
+        VH_HIP(hipMemcpyAsync(d_cap2, rp.cap2.data(), 4 * P2, hipMemcpyHostToDevice, st));
+        VH_HIP(hipMemcpyAsync(d_u2, rp.units_b.data(), sizeof(HashUnit) * P2, hipMemcpyHostToDevice, st));
         RepartParams rq{};
         rq.S = S_sub;
         rq.p_log2 = p_log2;
@@ -2162,14 +1946,13 @@ static void update_device(vh_hashagg *h, HaScratch &S, const void *keys, const v
         hpb.ent = S.entries2.ptr;
         for (int v = 0; v < HA_MAX_V; v++) hpb.vbits[v] = rq.vbits[v];
         d_units_b = d_u2;
-    } else {
-        units_b = units;
+        units_b = &rp.units_b;
     }
     {
         TimedScope ts("ha_reduce");
         const HaParams &hp = hpb;
-        const HaUnit *d_units = d_units_b;
-        const std::vector<HaUnit> &units = units_b;
+        const HashUnit *d_units = d_units_b;
+        const std::vector<HashUnit> &units = *units_b;
         dispatch_kb(h->key_dtype, [&](auto kbc) {
             using KB = decltype(kbc);
             dispatch_nv(nv, [&](auto nvc) {

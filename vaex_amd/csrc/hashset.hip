@@ -27,6 +27,7 @@
 
 #include "common.hpp"
 #include "hashset.hpp"
+#include "lds_table.hpp"
 
 using namespace vh;
 
@@ -94,8 +95,6 @@ constexpr int SI_SAMPLE_BLOCKS = 128;
 constexpr uint32_t SI_DEST_OVER = 0x80000000u;
 constexpr uint32_t SI_ROW_NONE = 0xffffffffu;
 
-template <typename T> using si_kb_t = std::conditional_t<sizeof(T) == 8, uint64_t, uint32_t>;
-
 struct SiParams {
     const void *keys;
     const uint8_t *mask, *select;
@@ -117,10 +116,6 @@ struct SiTable {
     uint32_t *wg_new;  // the workgroup's LDS count of keys it inserted (added to C_DISTINCT once)
 };
 
-struct SiUnit {
-    uint32_t bucket, w_begin, w_end, pad;
-};
-
 // top p_log2 bits of the key hash's high word (fine histogram: top SI_FINE_LOG2 bits)
 __device__ inline uint32_t si_h32(uint64_t kb) { return (uint32_t)(hash64(kb) >> 32); }
 __device__ inline uint32_t si_bucket(uint64_t kb, uint32_t p_log2) {
@@ -133,42 +128,13 @@ __device__ inline uint32_t si_bucket(uint64_t kb, uint32_t p_log2) {
 // the host grows the table and re-runs the chunk.  New keys are counted per workgroup in
 // LDS (one global add per workgroup: one counter bumped by every new key serialises).
 __device__ inline void si_global(const SiTable &g, uint64_t kb, uint64_t row) {
-    uint64_t pos = hash64(kb) & g.cap_mask;
-    for (int p = 0; p <= SET_MAX_PROBE; p++) {
-        const uint64_t k = __hip_atomic_load(&g.tab[2 * pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool mine = k == kb;
-        if (!mine && k == SET_EMPTY) {
-            const uint64_t old = atomicCAS((unsigned long long *)&g.tab[2 * pos], (unsigned long long)SET_EMPTY,
-                                           (unsigned long long)kb);
-            if (old == SET_EMPTY) atomicAdd(g.wg_new, 1u);
-            mine = old == SET_EMPTY || old == kb;
-        }
-        if (mine) {
-            if (__hip_atomic_load(&g.tab[2 * pos + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > row)
-                atomicMin((unsigned long long *)&g.tab[2 * pos + 1], (unsigned long long)row);
-            return;
-        }
-        pos = (pos + 1) & g.cap_mask;
-    }
-    atomicOr((unsigned long long *)&g.ctr[C_OVERFLOW], 1ULL);
+    set_claim(g.tab, g.cap_mask, SET_MAX_PROBE, kb, g.wg_new, &g.ctr[C_OVERFLOW], [&](uint64_t *first) {
+        if (__hip_atomic_load(first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > row)
+            atomicMin((unsigned long long *)first, (unsigned long long)row);
+    });
 }
 
 // ---- LDS dedup table: key bits -> smallest row (chunk-relative) ---------------------------
-// LDS slot hash: a 32-bit mixer (murmur3 fmix32), cheaper than hash64's 64-bit multiplies;
-// independent of the bucket bits (which come from hash64)
-__device__ inline uint32_t si_lds_hash(uint64_t kb) {
-    uint32_t h = (uint32_t)kb ^ (uint32_t)(kb >> 32) * 0x9e3779b9u;
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-template <typename KB> __host__ __device__ constexpr KB si_empty() { return ~KB(0); }
-template <typename KB> __host__ __device__ constexpr KB si_closed() { return ~KB(0) - 1; }
-
 template <typename KB> struct SiLds {
     KB *keys;        // [SI_LT]
     uint32_t *rows;  // [SI_LT + 2]: +2 side records for the keys equal to CLOSED / EMPTY
@@ -187,114 +153,37 @@ template <typename KB> __device__ inline SiLds<KB> si_lt_layout(unsigned char *r
 
 template <typename KB> __device__ inline void si_lt_init(const SiLds<KB> &t, int nthreads) {
     for (uint32_t i = threadIdx.x; i < SI_LT + 2; i += nthreads) {
-        if (i < SI_LT) t.keys[i] = si_empty<KB>();
+        if (i < SI_LT) t.keys[i] = kb_empty<KB>();
         t.rows[i] = SI_ROW_NONE;
     }
     if (threadIdx.x == 0) *t.used = 0;
 }
 
-template <typename KB> struct alignas(16) SiKB4 {
-    KB v[4];
+// hashset's two-choice table (lds_table.hpp): g1 from the key's LDS hash, g2 from a
+// multiply-shift of it; a row's payload is its chunk-relative row number, and a slot keeps
+// the smallest (ds_min); a spilled row goes to the HBM table with atomicMin of the row
+template <typename KB_> struct SiLt {
+    using KB = KB_;
+    static constexpr uint32_t SLOTS = SI_LT;
+    const SiLds<KB> &t;
+    const SiTable &g;
+    uint64_t row0;
+    __device__ KB *keys() const { return t.keys; }
+    __device__ void groups(KB kb, uint32_t &g1, uint32_t &g2) const {
+        const uint32_t h = lds_hash((uint64_t)kb);
+        g1 = (h & (SI_LT - 1)) >> 2;
+        g2 = ((h ^ 0x9e3779b9u) * 0x2545f491u) >> (32 - (SI_LT_LOG2 - 2));  // multiply-shift: top bits
+    }
+    __device__ void hit(uint32_t slot, uint32_t row) const { atomicMin(&t.rows[slot], row); }
+    __device__ void spill(KB kb, uint32_t row) const { si_global(g, (uint64_t)kb, row0 + row); }
 };
-
-__device__ inline uint32_t si_cas(uint32_t *p, uint32_t cmp, uint32_t val) { return atomicCAS(p, cmp, val); }
-__device__ inline uint64_t si_cas(uint64_t *p, uint64_t cmp, uint64_t val) {
-    return atomicCAS(reinterpret_cast<unsigned long long *>(p), (unsigned long long)cmp, (unsigned long long)val);
-}
-
-// Two-choice LDS table (as hashagg.hip's pass B): a key lives in one of two 4-slot groups,
-// g1 from its LDS hash and g2 from a second mix, both read at once (one ds_read_b128 each
-// for 4-byte keys), so a hit almost never needs a second round trip; one-group linear
-// probing displaced a few per cent of the keys, whose probe chains serialised every wave.
-// A new key is CASed into the first EMPTY slot of the group with more room.  Two lanes that
-// insert one key at once may place it in both groups: harmless, both records merge into the
-// key's one HBM slot with atomicMin of the row.  A key whose groups are both full goes to
-// the HBM table directly; keys whose bits are the top two patterns use the side records.
-template <typename KB> __device__ inline void si_lt2_groups(KB kb, uint32_t &g1, uint32_t &g2) {
-    const uint32_t h = si_lds_hash((uint64_t)kb);
-    g1 = (h & (SI_LT - 1)) >> 2;
-    g2 = ((h ^ 0x9e3779b9u) * 0x2545f491u) >> (32 - (SI_LT_LOG2 - 2));  // multiply-shift: top bits
-}
-
-template <typename KB>
-__device__ inline uint32_t si_lt2_find(const SiKB4<KB> &q1, const SiKB4<KB> &q2, uint32_t g1, uint32_t g2, KB kb) {
-    uint32_t slot = ~0u;
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-        if (q2.v[j] == kb) slot = 4 * g2 + j;
-        if (q1.v[j] == kb) slot = 4 * g1 + j;
-    }
-    return slot;
-}
-
-template <typename KB>
-__device__ inline void si_lt2_insert(const SiLds<KB> &t, const SiTable &g, uint64_t row0, KB kb, uint32_t row) {
-    constexpr KB EMPTY = si_empty<KB>();
-    uint32_t g1, g2;
-    si_lt2_groups(kb, g1, g2);
-    for (int it = 0; it < 64; it++) {
-        const SiKB4<KB> q1 = *reinterpret_cast<const SiKB4<KB> *>(t.keys + 4 * g1);
-        const SiKB4<KB> q2 = *reinterpret_cast<const SiKB4<KB> *>(t.keys + 4 * g2);
-        const uint32_t hit = si_lt2_find(q1, q2, g1, g2, kb);
-        if (hit != ~0u) {
-            atomicMin(&t.rows[hit], row);
-            return;
-        }
-        int e1 = 0, e2 = 0, f1 = -1, f2 = -1;
-#pragma unroll
-        for (int j = 3; j >= 0; j--) {
-            if (q1.v[j] == EMPTY) {
-                e1++;
-                f1 = j;
-            }
-            if (q2.v[j] == EMPTY) {
-                e2++;
-                f2 = j;
-            }
-        }
-        if (e1 == 0 && e2 == 0) break;
-        const uint32_t pos = e1 >= e2 ? 4 * g1 + f1 : 4 * g2 + f2;
-        const KB cur = si_cas(&t.keys[pos], EMPTY, kb);
-        if (cur == EMPTY || cur == kb) {
-            atomicMin(&t.rows[pos], row);
-            return;
-        }
-    }
-    si_global(g, (uint64_t)kb, row0 + row);
-}
-
-// M entries at once: both group reads of every entry issued before any is used, hits take
-// their ds_min right away, only keys new to the table take si_lt2_insert
-template <typename KB, int M>
-__device__ inline void si_lt_add_many(const SiLds<KB> &t, const SiTable &g, uint64_t row0, const KB *kb,
-                                      const uint32_t *row, const bool *valid) {
-    SiKB4<KB> q1[M], q2[M];
-    uint32_t g1[M], g2[M];
-#pragma unroll
-    for (int i = 0; i < M; i++) {
-        si_lt2_groups(kb[i], g1[i], g2[i]);
-        q1[i] = *reinterpret_cast<const SiKB4<KB> *>(t.keys + 4 * g1[i]);
-        q2[i] = *reinterpret_cast<const SiKB4<KB> *>(t.keys + 4 * g2[i]);
-    }
-    bool slow[M];
-#pragma unroll
-    for (int i = 0; i < M; i++) {
-        uint32_t slot = si_lt2_find(q1[i], q2[i], g1[i], g2[i], kb[i]);
-        if (kb[i] >= si_closed<KB>()) slot = SI_LT + (uint32_t)(kb[i] - si_closed<KB>());
-        slow[i] = valid[i] && slot == ~0u;
-        if (valid[i] && slot != ~0u) atomicMin(&t.rows[slot], row[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < M; i++)
-        if (slow[i]) si_lt2_insert<KB>(t, g, row0, kb[i], row[i]);
-}
 
 // every key the LDS table holds, with its smallest row, into the HBM table (after a barrier)
 template <typename KB> __device__ inline void si_lt_merge(const SiLds<KB> &t, const SiTable &g, uint64_t row0, int nthreads) {
     for (uint32_t i = threadIdx.x; i < SI_LT + 2; i += nthreads) {
         const uint32_t r = t.rows[i];
         if (r == SI_ROW_NONE) continue;
-        const KB kb = i < SI_LT ? t.keys[i] : (KB)(si_closed<KB>() + (i - SI_LT));
+        const KB kb = i < SI_LT ? t.keys[i] : (KB)(kb_closed<KB>() + (i - SI_LT));
         si_global(g, (uint64_t)kb, row0 + r);
     }
 }
@@ -328,7 +217,7 @@ __device__ inline void si_special_flush(const SiSpecial *sp, uint64_t row0, uint
 
 // classify row i (chunk-relative): returns true with its key bits when it is a regular key
 template <typename T>
-__device__ inline bool si_row(const SiParams &sp, uint64_t i, SiSpecial *spec, si_kb_t<T> *kb) {
+__device__ inline bool si_row(const SiParams &sp, uint64_t i, SiSpecial *spec, kb_t<T> *kb) {
     if (sp.select && !sp.select[i]) return false;  // filtered out / not selected
     if (sp.mask && sp.mask[i]) {
         atomicMin(&spec->null_first, (uint32_t)i);
@@ -346,7 +235,7 @@ __device__ inline bool si_row(const SiParams &sp, uint64_t i, SiSpecial *spec, s
         atomicMin(&spec->spec_first, (uint32_t)i);
         return false;
     }
-    *kb = (si_kb_t<T>)b;
+    *kb = (kb_t<T>)b;
     return true;
 }
 
@@ -367,62 +256,19 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_sample(SiParams sp, uint64_t 
         const uint64_t lin = blockIdx.x * (uint64_t)SI_BATCH + r;
         if ((uint64_t)gridDim.x * SI_BATCH >= sp.n && lin >= sp.n) break;
         const uint64_t i = (uint64_t)gridDim.x * SI_BATCH >= sp.n ? lin : hash64(block_stride * 0x9E3779B97F4A7C15ULL + lin) % sp.n;
-        si_kb_t<T> kb;
+        kb_t<T> kb;
         if (!si_row<T>(sp, i, &spec, &kb)) continue;
         atomicAdd(&h[si_h32(kb) >> (32 - SI_FINE_LOG2)], 1u);
-        uint64_t pos = hash64(kb) & smask;
-        for (int p = 0; p < 1 << 14; p++) {
-            uint64_t cur = __hip_atomic_load(&skeys[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == SET_EMPTY)
-                cur = atomicCAS((unsigned long long *)&skeys[pos], (unsigned long long)SET_EMPTY, (unsigned long long)kb);
-            if (cur == SET_EMPTY || cur == (uint64_t)kb) {
-                atomicAdd(&scnt[pos], 1u);
-                break;
-            }
-            pos = (pos + 1) & smask;
-        }
+        sample_insert(skeys, scnt, smask, (uint64_t)kb);
     }
     __syncthreads();
     for (uint32_t t = threadIdx.x; t < (1u << SI_FINE_LOG2); t += SI_THREADS)
         if (h[t]) atomicAdd(&fine_hist[t], (unsigned long long)h[t]);
 }
 
-// distinct keys of the sample, and how many were seen once / twice (Chao1 inputs)
-__global__ __launch_bounds__(256) void k_si_sample_stats(const uint32_t *scnt, uint64_t slots, unsigned long long *stats) {
-    __shared__ uint32_t part[3][4];
-    uint32_t d = 0, f1 = 0, f2 = 0;
-    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * 256) {
-        const uint32_t c = scnt[i];
-        d += c != 0;
-        f1 += c == 1;
-        f2 += c == 2;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        d += __shfl_down(d, off, 64);
-        f1 += __shfl_down(f1, off, 64);
-        f2 += __shfl_down(f2, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {  // one atomic per block and counter, not per wave
-        part[0][threadIdx.x >> 6] = d;
-        part[1][threadIdx.x >> 6] = f1;
-        part[2][threadIdx.x >> 6] = f2;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const uint32_t v = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
-        if (v) atomicAdd(&stats[threadIdx.x], (unsigned long long)v);
-    }
-}
-
 // ---- pass A -------------------------------------------------------------------------------
 __host__ __device__ constexpr size_t si_scatter_lds_bytes(uint32_t P) {
     return (size_t)(8 + 4 + 4) * (SI_BATCH + 1) + 16 * ((size_t)P + 1) + 64;
-}
-
-__device__ inline void si_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 __device__ inline void si_new_init(uint32_t *s_new) {
@@ -435,7 +281,7 @@ __device__ inline void si_new_flush(const uint32_t *s_new, uint64_t *ctr) {
 
 template <typename T>
 __global__ __launch_bounds__(SI_THREADS) void k_si_scatter(SiParams sp, SiTable g) {
-    using KB = si_kb_t<T>;
+    using KB = kb_t<T>;
     extern __shared__ __align__(16) unsigned char lds_raw[];
     __shared__ SiSpecial spec;
     __shared__ uint32_t s_total, s_over, s_new;
@@ -481,7 +327,7 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter(SiParams sp, SiTable 
             }
         }
         // exclusive scan of the bucket histogram
-        si_lds_barrier();
+        lds_barrier();
         {
             const uint32_t per = (P + SI_THREADS - 1) / SI_THREADS;
             const uint32_t t0 = threadIdx.x * per;
@@ -493,7 +339,7 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter(SiParams sp, SiTable 
                 if (lane >= off) inc += y;
             }
             if (lane == 63) wave_sums[wave] = inc;
-            si_lds_barrier();
+            lds_barrier();
             uint32_t wave_base = 0, total = 0;
             for (int k = 0; k < SI_THREADS / 64; k++) {
                 if (k < wave) wave_base += wave_sums[k];
@@ -509,7 +355,7 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter(SiParams sp, SiTable 
                 s_over = 0;
             }
         }
-        si_lds_barrier();
+        lds_barrier();
         bool over = false;
 #pragma unroll
         for (int r = 0; r < SI_RPT; r++) {
@@ -524,7 +370,7 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter(SiParams sp, SiTable 
             srow[pos] = (uint32_t)(b0 + (uint64_t)r * SI_THREADS + threadIdx.x);
         }
         if (over) s_over = 1;
-        si_lds_barrier();
+        lds_barrier();
         const uint32_t tot = s_total;
         for (uint32_t k = threadIdx.x; k < tot; k += SI_THREADS) {
             const uint32_t dst = sdst[k];
@@ -544,12 +390,12 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter(SiParams sp, SiTable 
                     novf++;
                 }
         }
-        si_lds_barrier();
+        lds_barrier();
         for (uint32_t t = threadIdx.x; t < P; t += SI_THREADS) {
             base[t] += hist[t];
             hist[t] = 0;
         }
-        si_lds_barrier();
+        lds_barrier();
     }
     if (novf) atomicAdd(&d_si_overflow_rows, (unsigned long long)novf);
     __syncthreads();
@@ -661,7 +507,7 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter4(SiParams sp, SiTable
                 rank[r] = ok ? (int32_t)rk : -1;
             }
         }
-        si_lds_barrier();
+        lds_barrier();
         if (threadIdx.x < 64) {
             const uint32_t lane = threadIdx.x;
             const uint32_t per = (P + 63) / 64;
@@ -686,7 +532,7 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter4(SiParams sp, SiTable
             if (lane == 0) hist[P] = 0;
             if (lane == 63) wave_sums[0] = inc;
         }
-        si_lds_barrier();
+        lds_barrier();
         const uint32_t tot = wave_sums[0];
 #pragma unroll
         for (int r = 0; r < SB * SI_RPT; r++) {
@@ -695,7 +541,7 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter4(SiParams sp, SiTable
             sk[pos] = kb[r];
             srow[pos] = (uint32_t)row_of(b0, r);
         }
-        si_lds_barrier();
+        lds_barrier();
         for (uint32_t k = threadIdx.x; k < tot; k += SI_THREADS) {
             const uint32_t key = sk[k], row = srow[k];
             const uint32_t t = si_bucket((uint64_t)key, sp.p_log2);
@@ -709,7 +555,7 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter4(SiParams sp, SiTable
         }
     }
     if (novf) atomicAdd(&d_si_overflow_rows, (unsigned long long)novf);
-    si_lds_barrier();
+    lds_barrier();
     for (uint32_t t = threadIdx.x; t < P; t += SI_THREADS) sp.fills[(uint64_t)t * sp.W + w] = base[t] - (uint32_t)sp.toff[t];
     si_special_flush(&spec, sp.row0, g.ctr);
     si_new_flush(&s_new, g.ctr);
@@ -717,14 +563,14 @@ __global__ __launch_bounds__(SI_THREADS) void k_si_scatter4(SiParams sp, SiTable
 
 // ---- pass B -------------------------------------------------------------------------------
 template <typename KB>
-__global__ __launch_bounds__(SB_THREADS) void k_si_reduce(SiParams sp, SiTable g, const SiUnit *units) {
+__global__ __launch_bounds__(SB_THREADS) void k_si_reduce(SiParams sp, SiTable g, const HashUnit *units) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     __shared__ uint32_t s_fill[1024];
     __shared__ uint32_t s_pre[1025];
     __shared__ uint32_t s_new;
     g.wg_new = &s_new;
     si_new_init(&s_new);
-    const SiUnit u = units[blockIdx.x];
+    const HashUnit u = units[blockIdx.x];
     const uint32_t b = u.bucket;
     const uint32_t cap = sp.cap[b];
     const uint32_t nw = u.w_end - u.w_begin;  // <= 1024 (host checks)
@@ -783,7 +629,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_si_reduce(SiParams sp, SiTable g
         } else {
             constexpr int MM = sizeof(KB) == 4 ? SB_M / 2 : SB_M / 4;  // 128 VGPRs at 1024 threads
 #pragma unroll
-            for (int h0 = 0; h0 < SB_M; h0 += MM) si_lt_add_many<KB, MM>(t, g, sp.row0, kb + h0, row + h0, valid + h0);
+            for (int h0 = 0; h0 < SB_M; h0 += MM) lt2_add_many<MM>(SiLt<KB>{t, g, sp.row0}, kb + h0, row + h0, valid + h0);
         }
     }
     __syncthreads();
@@ -795,7 +641,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_si_reduce(SiParams sp, SiTable g
 // ---- direct (P == 1): each workgroup dedups its row range of the raw keys -----------------
 template <typename T>
 __global__ __launch_bounds__(SB_THREADS) void k_si_direct(SiParams sp, SiTable g) {
-    using KB = si_kb_t<T>;
+    using KB = kb_t<T>;
     extern __shared__ __align__(16) unsigned char lds_raw[];
     __shared__ SiSpecial spec;
     __shared__ uint32_t s_new;
@@ -819,7 +665,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_si_direct(SiParams sp, SiTable g
             row[r] = (uint32_t)i;
             valid[r] = i < row_end && si_row<T>(sp, i, &spec, &kb[r]);
         }
-        si_lt_add_many<KB, U>(t, g, sp.row0, kb, row, valid);
+        lt2_add_many<U>(SiLt<KB>{t, g, sp.row0}, kb, row, valid);
     }
     __syncthreads();
     si_lt_merge<KB>(t, g, sp.row0, SB_THREADS);
@@ -1197,18 +1043,6 @@ static SiScratch &si_scratch() {
     return *p;
 }
 
-static uint64_t si_next_pow2(uint64_t x) {
-    uint64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
-static int si_blocks_per_cu(const void *kernel, int threads, size_t lds) {
-    int nb = 0;
-    VH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds));
-    return std::max(1, nb);
-}
-
 // one chunk of rows (device-resident, < 2^32) into the set; rows numbered from row0
 static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *mask, const uint8_t *select, uint64_t n,
                      uint64_t row0) {
@@ -1225,42 +1059,32 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
     if (const char *dbg = getenv("VH_SI_DEBUG")) sp.debug = (uint32_t)atoi(dbg);
 #endif
     // ---- sample: fine bucket histogram + distinct estimate, read back with the counters
-    const uint64_t sslots = 1ull << 21;
-    const uint64_t nbatch = (n + SI_BATCH - 1) / SI_BATCH;
-    const uint64_t sblocks = std::min<uint64_t>(nbatch, SI_SAMPLE_BLOCKS);
-    const uint64_t bstride = std::max<uint64_t>(SI_BATCH, n / sblocks);
-    const uint32_t FINE = 1u << SI_FINE_LOG2;
-    S.sample.ensure(sslots * 12 + 8 * FINE + 64);
-    uint64_t *skeys = S.sample.as<uint64_t>();
-    uint32_t *scnt = reinterpret_cast<uint32_t *>(skeys + sslots);
-    unsigned long long *fine = reinterpret_cast<unsigned long long *>(scnt + sslots);
-    unsigned long long *stats = fine + FINE;
-    VH_HIP(hipMemsetAsync(skeys, 0xff, 8 * sslots, st));
-    VH_HIP(hipMemsetAsync(scnt, 0, 4 * sslots + 8 * FINE + 64, st));
+    static_assert(SI_BATCH == HP_BATCH && SI_FINE_LOG2 == HP_FINE_LOG2 && SI_DEST_OVER == HP_DEST_OVER, "hash_plan.hpp");
+    const uint64_t sslots = HP_SAMPLE_SLOTS;
+    const uint32_t FINE = HP_FINE;
+    const HashSampleGeom sg = hash_sample_geom(n, SI_SAMPLE_BLOCKS);
+    const SampleBuf smp = sample_reset(S.sample, st);
     {
         TimedScope ts("set_sample");
         VH_DISPATCH_DTYPE(s->dtype, T,
-                          hipLaunchKernelGGL(k_si_sample<T>, dim3(sblocks), dim3(SI_THREADS), 0, st, sp, bstride, fine,
-                                             skeys, scnt, sslots - 1));
-        hipLaunchKernelGGL(k_si_sample_stats, dim3(blocks_for(sslots, 256, 4)), dim3(256), 0, st, scnt, sslots, stats);
+                          hipLaunchKernelGGL(k_si_sample<T>, dim3(sg.sblocks), dim3(SI_THREADS), 0, st, sp, sg.bstride, smp.fine,
+                                             smp.skeys, smp.scnt, sslots - 1));
+        hipLaunchKernelGGL(k_sample_stats<SampleCounts>, dim3(blocks_for(sslots, 256, 4)), dim3(256), 0, st,
+                           SampleCounts{smp.scnt}, sslots, smp.stats);
         VH_HIP(hipGetLastError());
     }
     std::vector<uint64_t> fh(FINE + 3), c(C_N);
-    VH_HIP(hipMemcpyAsync(fh.data(), fine, 8 * (FINE + 3), hipMemcpyDeviceToHost, st));
+    VH_HIP(hipMemcpyAsync(fh.data(), smp.fine, 8 * (FINE + 3), hipMemcpyDeviceToHost, st));
     VH_HIP(hipMemcpyAsync(c.data(), s->ctr.ptr, 8 * C_N, hipMemcpyDeviceToHost, st));
     VH_HIP(hipStreamSynchronize(st));
-    uint64_t sampled = 0;
-    for (uint32_t i = 0; i < FINE; i++) sampled += fh[i];
-    const double ds = (double)fh[FINE], f1 = (double)fh[FINE + 1], f2 = (double)fh[FINE + 2];
-    double dest;
-    if (sampled >= n || sblocks == nbatch) dest = ds;  // every row sampled: exact
-    else dest = f2 > 0 ? ds + f1 * f1 / (2 * f2) : ds + f1 * (f1 - 1) / 2;  // Chao1
-    dest = std::min<double>(std::max(dest, 1.0), (double)n);
+    const uint64_t sampled = hash_sampled_rows(fh.data());
+    // a sample whose blocks covered every batch is taken as exact; at least one key
+    const double dest = hash_estimate_keys(sampled, (double)fh[FINE], (double)fh[FINE + 1], (double)fh[FINE + 2], n,
+                                           /*whole_chunk=*/sg.sblocks == sg.nbatch, /*at_least_one=*/true);
     // the HBM table at <= 1/2 load for what it holds plus the estimate
     const uint64_t need = c[C_DISTINCT] + (uint64_t)dest;
-    if (2 * need > s->cap) set_grow(s, si_next_pow2(2 * need));
-    uint32_t p_log2 = 0;
-    while (p_log2 < SI_MAX_P_LOG2 && dest / (double)(1u << p_log2) > SI_TARGET_KEYS) p_log2++;
+    if (2 * need > s->cap) set_grow(s, next_pow2(2 * need));
+    const uint32_t p_log2 = hash_p_log2(dest, SI_TARGET_KEYS, SI_MAX_P_LOG2);
     sp.p_log2 = p_log2;
     sp.P = 1u << p_log2;
     const uint32_t P = sp.P;
@@ -1268,9 +1092,8 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
 
     const bool plain = (s->dtype == VH_I32 || s->dtype == VH_U32) && !mask && !select && n % 4 == 0 &&
                        (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
-    std::vector<SiUnit> units;
-    std::vector<uint32_t> cap;
-    std::vector<uint64_t> toff;
+    HashPlan pl;
+    const std::vector<HashUnit> &units = pl.units;
     uint32_t W = 0;
     int fast_sb = 0;
     size_t lds_scatter = 0;
@@ -1308,8 +1131,7 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
         }
     };
     if (P > 1) {
-        std::vector<uint64_t> bh(P, 0);
-        for (uint32_t i = 0; i < FINE; i++) bh[i >> (SI_FINE_LOG2 - p_log2)] += fh[i];
+        const std::vector<uint64_t> bh = hash_fold_fine(fh.data(), p_log2);
         // keys of <= 4 bytes take the multi-batch pass A (k_si_scatter4) with as many
         // batches per commit as the LDS holds (VH_SI_FAST=0: the one-batch kernel, A/B runs)
         static const bool fast_on = [] {
@@ -1332,52 +1154,27 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
         lds_scatter = lds_a;
         int bpc = 1;
         if (fast_sb)
-            with_fast([&](auto kernel) { bpc = si_blocks_per_cu(reinterpret_cast<const void *>(kernel), SI_THREADS, lds_a); });
+            with_fast([&](auto kernel) { bpc = blocks_per_cu(reinterpret_cast<const void *>(kernel), SI_THREADS, lds_a); });
         else
             VH_DISPATCH_DTYPE(s->dtype, T,
-                              bpc = si_blocks_per_cu(reinterpret_cast<const void *>(k_si_scatter<T>), SI_THREADS, lds_a));
-        bpc = std::min(bpc, 4);
-        W = std::min<uint32_t>(1024, (uint32_t)cu_count() * bpc);
-        // pass-A workgroup w takes batches w, w + W, ...: at most ceil(batches / W) of them
-        const uint64_t rows_per_wg = (nbatch + W - 1) / W * SI_BATCH;
-        cap.resize(P);
-        toff.resize(P);
-        uint64_t stride = 0;
-        for (uint32_t t = 0; t < P; t++) {
-            const double e = (double)rows_per_wg * (double)bh[t] / (double)std::max<uint64_t>(sampled, 1);
-            uint64_t cc = (uint64_t)(e * 1.04 + 6.0 * std::sqrt(e + 1.0)) + 32;
-            cc = std::min<uint64_t>((cc + 7) & ~uint64_t(7), rows_per_wg + 8);
-            cap[t] = (uint32_t)cc;
-            toff[t] = stride;
-            stride += cc;
-        }
-        if (stride + rows_per_wg >= (uint64_t)SI_DEST_OVER) fail(VH_ERR_RUNTIME, "ordered_set: region table too large");
-        const uint64_t total = stride * W;
+                              bpc = blocks_per_cu(reinterpret_cast<const void *>(k_si_scatter<T>), SI_THREADS, lds_a));
+        if (!hash_plan_partition(n, cu_count(), bpc, p_log2, bh, sampled, pl)) fail(VH_ERR_RUNTIME, "ordered_set: region table too large");
+        W = pl.W;
+        const uint64_t total = pl.stride * W;
         S.ent.ensure(8 * total + 64);
         if (kbs == 8) S.ent_row.ensure(4 * total + 64);
-        // pass-B units: a unit merges each of its keys into the HBM table once, so split a
-        // bucket over ranges of workgroups only as far as the CUs need work
-        const double target = std::max(1.0, (double)n / ((double)cu_count() * 2));
-        for (uint32_t t = 0; t < P; t++) {
-            const double e = (double)n * (double)bh[t] / (double)std::max<uint64_t>(sampled, 1);
-            const uint32_t gq = (uint32_t)std::min<double>(W, std::max(1.0, std::ceil(e / target)));
-            for (uint32_t k = 0; k < gq; k++)
-                units.push_back({t, (uint32_t)((uint64_t)W * k / gq), (uint32_t)((uint64_t)W * (k + 1) / gq), 0});
-        }
-        const uint64_t meta_bytes = 8 * (uint64_t)P + sizeof(SiUnit) * units.size() + 4 * (uint64_t)P +
-                                    4 * (uint64_t)P * W + 256;
-        S.meta.ensure(meta_bytes);
+        S.meta.ensure(pl.meta.bytes);
         unsigned char *mb = S.meta.as<unsigned char>();
-        uint64_t *d_toff = reinterpret_cast<uint64_t *>(mb);
-        SiUnit *d_units = reinterpret_cast<SiUnit *>(d_toff + P);
-        uint32_t *d_cap = reinterpret_cast<uint32_t *>(d_units + units.size());
-        uint32_t *d_fills = d_cap + P;
-        VH_HIP(hipMemcpyAsync(d_toff, toff.data(), 8 * (uint64_t)P, hipMemcpyHostToDevice, st));
-        VH_HIP(hipMemcpyAsync(d_units, units.data(), sizeof(SiUnit) * units.size(), hipMemcpyHostToDevice, st));
-        VH_HIP(hipMemcpyAsync(d_cap, cap.data(), 4 * (uint64_t)P, hipMemcpyHostToDevice, st));
+        uint64_t *d_toff = reinterpret_cast<uint64_t *>(mb + pl.meta.toff);
+        HashUnit *d_units = reinterpret_cast<HashUnit *>(mb + pl.meta.units);
+        uint32_t *d_cap = reinterpret_cast<uint32_t *>(mb + pl.meta.cap);
+        uint32_t *d_fills = reinterpret_cast<uint32_t *>(mb + pl.meta.fills);
+        VH_HIP(hipMemcpyAsync(d_toff, pl.toff.data(), 8 * (uint64_t)P, hipMemcpyHostToDevice, st));
+        VH_HIP(hipMemcpyAsync(d_units, units.data(), sizeof(HashUnit) * units.size(), hipMemcpyHostToDevice, st));
+        VH_HIP(hipMemcpyAsync(d_cap, pl.cap.data(), 4 * (uint64_t)P, hipMemcpyHostToDevice, st));
         sp.W = W;
-        sp.rows_per_wg = rows_per_wg;
-        sp.wg_stride = stride;
+        sp.rows_per_wg = pl.rows_per_wg;
+        sp.wg_stride = pl.stride;
         sp.cap = d_cap;
         sp.toff = d_toff;
         sp.fills = d_fills;
@@ -1390,12 +1187,11 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
             TimedScope ts("set_insert");
             int bpc = 1;
             VH_DISPATCH_DTYPE(s->dtype, T,
-                              bpc = si_blocks_per_cu(reinterpret_cast<const void *>(k_si_direct<T>), SB_THREADS, lt_lds));
-            const uint64_t Wd = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cu_count() * bpc,
-                                                                          (n + 4 * SB_THREADS - 1) / (4 * SB_THREADS)));
-            sp.rows_per_wg = (n + Wd - 1) / Wd;
+                              bpc = blocks_per_cu(reinterpret_cast<const void *>(k_si_direct<T>), SB_THREADS, lt_lds));
+            const HashDirect d = hash_plan_direct(n, cu_count(), bpc, SB_THREADS);
+            sp.rows_per_wg = d.rows_per_wg;
             VH_DISPATCH_DTYPE(s->dtype, T,
-                              hipLaunchKernelGGL(k_si_direct<T>, dim3((unsigned)Wd), dim3(SB_THREADS), lt_lds, st, sp, g));
+                              hipLaunchKernelGGL(k_si_direct<T>, dim3((unsigned)d.W), dim3(SB_THREADS), lt_lds, st, sp, g));
             VH_HIP(hipGetLastError());
         } else {
             {
@@ -1412,7 +1208,7 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
             }
             {
                 TimedScope ts("set_reduce");
-                const SiUnit *d_units = reinterpret_cast<const SiUnit *>(S.meta.as<uint64_t>() + P);
+                const HashUnit *d_units = reinterpret_cast<const HashUnit *>(S.meta.as<unsigned char>() + pl.meta.units);
                 if (kbs == 8)
                     hipLaunchKernelGGL(k_si_reduce<uint64_t>, dim3((unsigned)units.size()), dim3(SB_THREADS), lt_lds, st,
                                        sp, g, d_units);
@@ -1425,7 +1221,7 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
         VH_HIP(hipMemcpyAsync(c.data(), s->ctr.ptr, 8 * C_N, hipMemcpyDeviceToHost, st));
         VH_HIP(hipStreamSynchronize(st));
         if (!c[C_OVERFLOW]) {
-            if (c[C_DISTINCT] * 2 > s->cap) set_grow(s, si_next_pow2(c[C_DISTINCT] * 2));
+            if (c[C_DISTINCT] * 2 > s->cap) set_grow(s, next_pow2(c[C_DISTINCT] * 2));
             break;
         }
         // the estimate missed: grow x4 and re-run the chunk (inserts are idempotent; the

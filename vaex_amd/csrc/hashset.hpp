@@ -1,5 +1,7 @@
 // GPU open-address hash set shared by hashset.hip (ordered_set) and the
-// fused set-ordinal binner in binning.hip.
+// fused set-ordinal binner in binning.hip; also what the hash engines (hashset.hip,
+// hashagg.hip, counter.hip) share in HBM: the slot claim of a {key, payload} table and the
+// key sample.  Their LDS table is lds_table.hpp, their host plan hash_plan.hpp.
 //
 // Layout in HBM: `tab[cap]` of 16-byte slots {key bits zero-extended (EMPTY = ~0),
 // first row the key was seen at (the ordinal order)}, so an insert probe and its
@@ -11,6 +13,7 @@
 // reference's nan_value/null_value (hash_primitives.hpp:436-450).
 #pragma once
 #include "common.hpp"
+#include "hash_plan.hpp"
 
 namespace vh {
 
@@ -40,6 +43,111 @@ template <typename T> __device__ inline uint64_t key_bits(T v) {
         uint8_t u;
         __builtin_memcpy(&u, &v, 1);
         return u;
+    }
+}
+
+// Claim the 16-byte {key, payload} slot of `kb` in an open-address HBM table `tab` (CAS on an
+// EMPTY key word, linear probing over at most max_probe + 1 slots) and call fold(payload word)
+// on it: the caller's atomicMin of a row or atomicAdd of a count.  A probe sequence that runs
+// out raises *overflow instead (the host grows the table and runs the chunk again).  New keys
+// are counted per workgroup in LDS (`wg_new`): one global counter bumped by every new key
+// serialises.
+template <typename Probe, typename Fold>
+__device__ inline void set_claim(uint64_t *tab, uint64_t cap_mask, Probe max_probe, uint64_t kb, uint32_t *wg_new,
+                                 uint64_t *overflow, Fold &&fold) {
+    uint64_t pos = hash64(kb) & cap_mask;
+    for (Probe p = 0; p <= max_probe; p++) {
+        const uint64_t k = __hip_atomic_load(&tab[2 * pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        bool mine = k == kb;
+        if (!mine && k == SET_EMPTY) {
+            const uint64_t old = atomicCAS((unsigned long long *)&tab[2 * pos], (unsigned long long)SET_EMPTY,
+                                           (unsigned long long)kb);
+            if (old == SET_EMPTY) atomicAdd(wg_new, 1u);
+            mine = old == SET_EMPTY || old == kb;
+        }
+        if (mine) {
+            fold(&tab[2 * pos + 1]);
+            return;
+        }
+        pos = (pos + 1) & cap_mask;
+    }
+    atomicOr((unsigned long long *)overflow, 1ULL);
+}
+
+// ---- the key sample of the hash engines (hashagg.hip, hashset.hip, counter.hip) -----------
+// one sampled key into the sample's HBM table: keys[smask + 1] (EMPTY = free) with a count of
+// its occurrences per slot; a key that finds no slot within the probe limit is not counted
+constexpr int SAMPLE_MAX_PROBE = 1 << 14;
+__device__ inline void sample_insert(uint64_t *skeys, uint32_t *scnt, uint64_t smask, uint64_t key) {
+    uint64_t pos = hash64(key) & smask;
+#pragma nounroll
+    for (int p = 0; p < SAMPLE_MAX_PROBE; p++) {
+        uint64_t cur = __hip_atomic_load(&skeys[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == SET_EMPTY)
+            cur = atomicCAS((unsigned long long *)&skeys[pos], (unsigned long long)SET_EMPTY, (unsigned long long)key);
+        if (cur == SET_EMPTY || cur == key) {
+            atomicAdd(&scnt[pos], 1u);
+            break;
+        }
+        pos = (pos + 1) & smask;
+    }
+}
+
+// the sample buffer (hash_sample_layout) ready for a sample on `st`: keys EMPTY, the rest zero
+struct SampleBuf {
+    uint64_t *skeys;
+    uint32_t *scnt;
+    unsigned long long *fine, *stats;
+};
+inline SampleBuf sample_reset(DevBuf &buf, hipStream_t st) {
+    const HashSampleLayout sl = hash_sample_layout();
+    buf.ensure(sl.bytes);
+    unsigned char *b = buf.as<unsigned char>();
+    VH_HIP(hipMemsetAsync(b + sl.skeys, 0xff, sl.scnt - sl.skeys, st));
+    VH_HIP(hipMemsetAsync(b + sl.scnt, 0, sl.bytes - sl.scnt, st));
+    return {reinterpret_cast<uint64_t *>(b + sl.skeys), reinterpret_cast<uint32_t *>(b + sl.scnt),
+            reinterpret_cast<unsigned long long *>(b + sl.fine), reinterpret_cast<unsigned long long *>(b + sl.stats)};
+}
+
+// occurrence counts of a sample table's slots (0 = free slot), as k_sample_stats reads them
+struct SampleCounts {  // a count array next to the keys
+    const uint32_t *cnt;
+    __device__ uint64_t operator()(uint64_t i) const { return cnt[i]; }
+};
+struct SampleSlotCounts {  // 16-byte {key, count} slots
+    const uint64_t *tab;
+    __device__ uint64_t operator()(uint64_t i) const {
+        const ulonglong2 e = reinterpret_cast<const ulonglong2 *>(tab)[i];
+        return e.x == SET_EMPTY ? 0 : e.y;
+    }
+};
+
+// distinct keys of the sample, and how many were seen once / twice (Chao1 inputs), added to
+// stats[0..2]
+template <typename Counts>
+__global__ __launch_bounds__(256) void k_sample_stats(Counts counts, uint64_t slots, unsigned long long *stats) {
+    __shared__ uint32_t part[3][4];
+    uint32_t d = 0, f1 = 0, f2 = 0;
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t c = counts(i);
+        d += c != 0;
+        f1 += c == 1;
+        f2 += c == 2;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        d += __shfl_down(d, off, 64);
+        f1 += __shfl_down(f1, off, 64);
+        f2 += __shfl_down(f2, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {  // one atomic per block and counter, not per wave
+        part[0][threadIdx.x >> 6] = d;
+        part[1][threadIdx.x >> 6] = f1;
+        part[2][threadIdx.x >> 6] = f2;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const uint32_t v = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
+        if (v) atomicAdd(&stats[threadIdx.x], (unsigned long long)v);
     }
 }
 
