@@ -313,6 +313,56 @@ int vh_dense_first_take(const void *keys, uint64_t n, int loc, int key_dtype, in
  * on up to `threads` threads */
 int vh_host_take(int ncols, void *const *dsts, const void *const *srcs, const int *itemsizes, const int64_t *idx,
                  uint64_t n, int threads);
+
+/* ---- index_hash_<dtype>: hash_primitives.hpp:623-900 (key -> first row, + duplicate rows) ---
+ * The hash map of DataFrame.join (join.py:124-292).  Key identity is the ordered set's: one
+ * NaN entry, one null entry (mask byte set), every other key by bit pattern.  initial_capacity:
+ * slots of the first table (a power of two >= 16), 0 = the default (then the table is also
+ * sized for the rows of each update before it runs); the table grows as needed. */
+typedef struct vh_index vh_index;
+int vh_index_create(int dtype, uint64_t initial_capacity, vh_index **out);
+int vh_index_destroy(vh_index *index);
+/* update(keys[, mask], start_index): row i of the chunk has row number start_index + i.  mask
+ * may be NULL (1 = null); select may be NULL, rows with select[i] == 0 are not seen at all.  A
+ * key maps to the smallest row it was seen at; its other rows are its duplicates.  nan_value /
+ * null_value are the largest NaN / null row over all updates -- one rule for every entry: row
+ * numbers decide, not the order of the calls (with rows fed in order this is add_nan / add_null
+ * overwriting, :652-660).  mask / select may be host or HBM pointers whatever `loc` says of the
+ * keys.  Fails once the index was probed (sealed). */
+int vh_index_update(vh_index *index, const void *keys, const uint8_t *mask, const uint8_t *select, uint64_t n,
+                    uint64_t start_index, int loc);
+/* merge (:850-894): every row `other` has seen is seen by `index` too, under the same row
+ * number.  Fails once either was probed (the rows an index has seen are dropped at seal). */
+int vh_index_merge(vh_index *index, vh_index *other);
+/* length = regular rows indexed (distinct keys + duplicate rows) + 1 if any NaN + 1 if any
+ * null (:636-645); nan_value / null_value are -1 when absent */
+int vh_index_info(vh_index *index, int64_t *length, int64_t *nan_count, int64_t *null_count, int64_t *nan_value,
+                  int64_t *null_value, int *has_duplicates);
+/* map_index / map_index_with_mask (:679-754): out[i] = first row of keys[i]; nan_value for NaN
+ * keys, null_value for mask[i] != 0 (mask may be NULL), -1 for unknown keys (and for NaN / null
+ * keys when the index holds none).  *found_unknown = 1 when any -1 was written.  out_itemsize 4
+ * or 8; 4 only while every row number is below 2^31.  The first probe seals the index. */
+int vh_index_map_index(vh_index *index, const void *keys, const uint8_t *mask, uint64_t n, int loc, void *out,
+                       int out_itemsize, int out_loc, int *found_unknown);
+/* map_index_duplicates (:756-848), in two calls.  With left_out = right_out = NULL: for every
+ * left row whose key has duplicate rows, one pair (start_index + i, duplicate row) per
+ * duplicate, in left-row order, duplicates ascending within a key (NaN and masked keys are
+ * skipped); the pairs stay in the library and *n_out is their number.  A second call with
+ * left_out / right_out (n_out items each, host or HBM; the other arguments are ignored) copies
+ * them out and drops them. */
+int vh_index_map_index_duplicates(vh_index *index, const void *keys, const uint8_t *mask, uint64_t n,
+                                  uint64_t start_index, int loc, uint64_t *n_out, int64_t *left_out, int64_t *right_out);
+/* device gather: dsts[c][i] = idx[i] >= 0 ? srcs[c][idx[i]] : 0 for ncols columns of
+ * itemsizes[c] (1/2/4/8) bytes, i < n; idx_itemsize 4 or 8 (signed); mask_out (may be NULL):
+ * mask_out[i] = idx[i] < 0.  Every buffer is in HBM; non-negative indices must be in range.
+ * Eight columns share one pass over idx. */
+int vh_take(int ncols, void *const *dsts, const void *const *srcs, const int *itemsizes, const void *idx,
+            int idx_itemsize, uint64_t n, uint8_t *mask_out);
+/* the inner join's compaction (join.py:215-220): the positions i with idx[i] >= 0, ascending,
+ * into left_rows_out (int64) and their idx[i] into idx_out (idx_itemsize bytes each); both
+ * have room for n items, *m are written.  Every buffer is in HBM. */
+int vh_index_matched(const void *idx, int idx_itemsize, uint64_t n, uint64_t *m, int64_t *left_rows_out, void *idx_out);
+
 /* ---- multi-GPU (comm.hip): RCCL bound by the library, one process per GPU ----------
  * The reference has no multi-process path; its ExecutorLocal reduces per-thread task
  * parts serially (execution.py:285, Aggregator::reduce superagg.cpp:160-167,205-212,

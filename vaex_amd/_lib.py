@@ -106,6 +106,15 @@ SIGNATURES = {
     "vh_dense_first_order": (_i32, [_vp, _u64, _i32, _i32, _i64, _u64, _vp, _u64, _vp]),
     "vh_dense_first_take": (_i32, [_vp, _u64, _i32, _i32, _i64, _u64, _vp, _i32, _u64, _i32, _vp, _vp, _vp, _i32, _vp]),
     "vh_host_take": (_i32, [_i32, _vp, _vp, _vp, _vp, _u64, _i32]),
+    "vh_index_create": (_i32, [_i32, _u64, _p(_vp)]),
+    "vh_index_destroy": (_i32, [_vp]),
+    "vh_index_update": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, _i32]),
+    "vh_index_merge": (_i32, [_vp, _vp]),
+    "vh_index_info": (_i32, [_vp, _p(_i64), _p(_i64), _p(_i64), _p(_i64), _p(_i64), _p(_i32)]),
+    "vh_index_map_index": (_i32, [_vp, _vp, _vp, _u64, _i32, _vp, _i32, _i32, _p(_i32)]),
+    "vh_index_map_index_duplicates": (_i32, [_vp, _vp, _vp, _u64, _u64, _i32, _p(_u64), _vp, _vp]),
+    "vh_take": (_i32, [_i32, _p(_vp), _p(_vp), _p(_i32), _vp, _i32, _u64, _vp]),
+    "vh_index_matched": (_i32, [_vp, _i32, _u64, _p(_u64), _vp, _vp]),
     "vh_combine_keys": (_i32, [_u64, _i32, _p(_vp), _p(_i32), _p(_i64), _p(_i64), _vp]),
     "vh_dense_rank_i64": (_i32, [_u64, _vp, _vp, _vp, _p(_u64)]),
     "vh_decode_keys": (_i32, [_u64, _vp, _vp, _i32, _p(_i64), _p(_i64), _p(_i64), _p(_i32), _p(_vp)]),

@@ -1013,6 +1013,55 @@ class DataFrame:
             return self.groupby(by, agg=agg, sort=sort, assume_sparse=assume_sparse, row_limit=row_limit,
                                 _speculate=False)
 
+    # ---- join ----------------------------------------------------------------------
+    def _index(self, expression, prime_growth=False, cardinality=None):
+        """dataframe.py:482-539: the GPU ``index_hash`` of an expression over all rows, built in
+        executor chunks (key -> first row, plus the other rows of duplicated keys).  A filter
+        goes in as the update's ``select``: filtered-out rows never enter, and row numbers stay
+        unfiltered row numbers.  ``cardinality`` only sizes the first table."""
+        from .join import index
+        return index(self, expression, prime_growth=prime_growth, cardinality=cardinality)
+
+    def take(self, indices, filtered=True, dropfilter=True):
+        """A new frame of the rows ``indices`` (a host array or a DeviceArray of int32 / int64):
+        HBM columns are gathered on the device (``vh_take``), host columns on the host threads;
+        virtual columns, variables and categories carry over.  On a filtered frame only
+        ``filtered=False, dropfilter=False`` is supported: the indices are unfiltered row
+        numbers and the filter stays on the result (the other forms raise NotImplementedError)."""
+        from .join import take
+        return take(self, indices, filtered=filtered, dropfilter=dropfilter)
+
+    def join(self, other, on=None, left_on=None, right_on=None, lprefix="", rprefix="", lsuffix="", rsuffix="",
+             how="left", allow_duplication=False, prime_growth=False, cardinality_other=None, inplace=False):
+        """DataFrame.join (join.py:124-292): attach the columns of ``other`` to the rows of this
+        frame whose ``left_on`` key equals ``other``'s ``right_on`` key (``on``: the same name
+        in both; no key at all: a row-wise merge of frames of equal length).
+
+        ``how`` is 'left', 'right' (the sides and their prefixes swap) or 'inner'.  Columns
+        present in both frames are renamed with the prefixes / suffixes (the join column is not
+        added twice); a collision without a proper prefix / suffix raises ValueError.  The key
+        dtypes must be equal (datetimes join as int64), else TypeError.  ``other`` is indexed on
+        the GPU (``_index``; its filter removes rows from the index), every unfiltered row of
+        this frame is mapped to its first matching row, and this frame's filter stays on the
+        result.  Duplicated keys in ``other`` raise ValueError unless ``allow_duplication``: then
+        the extra matches are appended after all original rows, in left-row order.
+        ``cardinality_other`` only sizes the index's first table.
+
+        Every column of ``other`` is gathered where it lives: HBM columns on the device (eight per
+        pass, int32 lookups while ``other`` has fewer than 2^31 rows), host columns on the host.
+        Keys compare by bit pattern with one NaN (``-0.0`` and ``0.0`` differ).
+
+        Limit: HBM frames carry no masks.  When a row of a 'left' / 'right' join finds no match,
+        the joined columns come back masked: host columns as ``np.ma`` arrays, and HBM columns
+        READ BACK to the host as ``np.ma`` arrays (with the mask the gather kernel built), so the
+        result is then a mixed host / HBM frame.  When every row matches, and always for
+        'inner', HBM columns stay in HBM.  A rename of a column that a virtual column, filter or
+        selection uses raises NotImplementedError (expressions are not rewritten)."""
+        from .join import join
+        return join(self, other, on=on, left_on=left_on, right_on=right_on, lprefix=lprefix, rprefix=rprefix,
+                    lsuffix=lsuffix, rsuffix=rsuffix, how=how, allow_duplication=allow_duplication,
+                    prime_growth=prime_growth, cardinality_other=cardinality_other, inplace=inplace)
+
     def export_hdf5(self, path, **kwargs):
         """dataframe.py export_hdf5: numeric columns (host or HBM) as vaex's HDF5 layout
         version 2, contiguous and 4 KiB aligned so the file maps back without copies."""

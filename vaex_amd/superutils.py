@@ -6,7 +6,10 @@ bindings ``hash_primitives.cpp:26-73``): ``update``, ``key_array``, ``map_ordina
 ``nan_value``/``null_value``, ``fingerprint``, ``len()``, the ``create`` constructor
 ``ordered_set_<t>(keys, null_value, nan_count, null_count, fingerprint)`` and
 ``flatten_values``.  ``counter_<dtype>`` (``hash_primitives.hpp:328-415``), the key -> count map
-of ``value_counts``, sits beside it over the library's hash counter.
+of ``value_counts``, sits beside it over the library's hash counter, and ``index_hash_<dtype>``
+(``hash_primitives.hpp:623-900``), the key -> row map of ``DataFrame.join``, over the library's
+index, with the device gather (``take_device``) and the inner join's compaction
+(``index_matched``) a join needs next to it.
 
 Ordinals are assigned in first-appearance order over all ``update`` calls -- what a
 single-threaded reference ``update`` with ``nmaps = 1`` produces.  (With threads the
@@ -332,9 +335,203 @@ class _CounterBase:
             self._handle = None
 
 
+# keys of <= 4 bytes the index probe's LDS route holds (index.hip IX_LDS_BYTES = 64 KiB = 8192
+# packed slots, at half load; 8-byte keys: half as many): up to this many distinct keys (in an update of as many rows) the
+# sealed lookup table is staged in LDS once per workgroup, past it the probe reads it from HBM
+INDEX_LDS_KEYS = 4096
+
+
+class _IndexHashBase:
+    """``index_hash_<dtype>`` (``hash_primitives.hpp:623-900``; bindings
+    ``hash_primitives.cpp:53-69``): key -> the first row it was seen at, plus the other rows
+    of duplicated keys, over the GPU index of libvaexhip -- the hash map of ``DataFrame.join``.
+
+    The contract is the single-threaded, one-map, rows-in-order reference: a key maps to its
+    first row, ``nan_value`` / ``null_value`` to the last NaN / null row.  Key identity is the
+    other GPU hash engines': by bit pattern, with one NaN entry, so ``-0.0`` and ``0.0`` are two
+    keys (the reference compares keys with ``==``).  ``map_index`` of a NaN / null key when the
+    index holds none gives ``-1`` (the reference leaves that entry uninitialised).  The first
+    probe seals the index: ``update`` and ``merge`` raise after it.
+    ``index_hash_<t>(initial_capacity=16)`` starts the table at 16 slots."""
+    _dtype = "int64"
+
+    def __init__(self, *args, initial_capacity=0):
+        h = ctypes.c_void_p()
+        _lib.call("vh_index_create", _lib.DTYPE_CODE[self._dtype], int(initial_capacity), ctypes.byref(h))
+        self._handle = h.value
+
+    # ---- building --------------------------------------------------------------
+    def _keys(self, ar):
+        if np.ma.isMaskedArray(ar):
+            ar = ar.data
+        if isinstance(ar, DeviceArray):
+            if ar.dtype.itemsize != np.dtype(self._dtype).itemsize:
+                raise TypeError(f"index_hash_{self._dtype} cannot take a {ar.dtype} column")
+            return ar
+        ar = np.asarray(ar)
+        if ar.dtype.kind in "mM":
+            ar = ar.view(np.int64)
+        return np.ascontiguousarray(ar, dtype=self._dtype)
+
+    def update(self, ar, *args, **kwargs):
+        """update(keys[, mask], start_index=0, select=None): row i is row ``start_index + i``;
+        rows where select == 0 are not seen at all."""
+        mask = None
+        rest = list(args)
+        if rest and (isinstance(rest[0], (np.ndarray, list, DeviceArray)) or rest[0] is None):
+            mask = rest.pop(0)
+        mask = kwargs.pop("mask", mask)
+        start_index = kwargs.pop("start_index", rest.pop(0) if rest else 0)
+        select = kwargs.pop("select", None)
+        if np.ma.isMaskedArray(ar):
+            m = np.ma.getmaskarray(ar)
+            mask = m if mask is None else (np.asarray(mask, bool) | m)
+        ar = self._keys(ar)
+        device = isinstance(ar, DeviceArray)
+        kptr, n, _, _, loc, keep = _column(ar)
+        mkeep, mptr = _CounterBase._side(mask, device)
+        skeep, sptr = _CounterBase._side(select, device)
+        if n:
+            _lib.call("vh_index_update", self._handle, kptr, mptr, sptr, n, int(start_index), loc)
+
+    def merge(self, other):
+        """index_hash::merge (hash_primitives.hpp:850-894): every row ``other`` has seen,
+        under the same row number.  Raises once either index was probed."""
+        _lib.call("vh_index_merge", self._handle, other._handle)
+
+    # ---- reading ---------------------------------------------------------------
+    def _info(self):
+        vals = [ctypes.c_int64() for _ in range(5)]
+        dup = ctypes.c_int()
+        _lib.call("vh_index_info", self._handle, *[ctypes.byref(v) for v in vals], ctypes.byref(dup))
+        return [v.value for v in vals] + [bool(dup.value)]
+
+    def __len__(self):
+        return self._info()[0]
+
+    def length(self):
+        return len(self)
+
+    nan_count = property(lambda self: self._info()[1])
+    null_count = property(lambda self: self._info()[2])
+    nan_value = property(lambda self: self._info()[3])
+    null_value = property(lambda self: self._info()[4])
+    has_nan = property(lambda self: self._info()[1] > 0)
+    has_null = property(lambda self: self._info()[2] > 0)
+    has_duplicates = property(lambda self: self._info()[5])
+
+    def _map(self, values, mask, out):
+        values = self._keys(values)
+        device = isinstance(values, DeviceArray)
+        n = len(values)
+        if out is None:
+            out = DeviceArray(n, np.int64) if device else np.empty(n, np.int64)
+        if len(out) != n:
+            raise ValueError("map_index: out and values differ in length")
+        odt = np.dtype(out.dtype)
+        if odt not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise TypeError("map_index: out must be int32 or int64")
+        if isinstance(out, DeviceArray):
+            optr, oloc = out.ptr, _lib.LOC_DEVICE
+        else:
+            if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable):
+                raise TypeError("map_index: out must be a contiguous writeable array")
+            optr, oloc = out.ctypes.data, _lib.LOC_HOST
+        mkeep, mptr = _CounterBase._side(mask, device)
+        if mkeep is not None and len(mkeep) != n:
+            raise ValueError("map_index: mask and values differ in length")
+        found = ctypes.c_int(0)
+        kptr = values.ptr if device else values.ctypes.data
+        _lib.call("vh_index_map_index", self._handle, kptr, mptr, n, _lib.LOC_DEVICE if device else _lib.LOC_HOST,
+                  optr, odt.itemsize, oloc, ctypes.byref(found))
+        return out, bool(found.value)
+
+    def map_index(self, values, out=None):
+        """key -> first row, -1 for unknown keys (hash_primitives.hpp:679-714).  Without ``out``
+        returns int64 (a DeviceArray for a DeviceArray of keys); with ``out`` (int32 / int64,
+        host or device) writes into it and returns whether any -1 was written."""
+        res, found = self._map(values, None, out)
+        return res if out is None else found
+
+    def map_index_masked(self, values, mask, out=None):
+        """map_index with a mask (1 = null -> null_value; hash_primitives.hpp:715-754)."""
+        res, found = self._map(values, mask, out)
+        return res if out is None else found
+
+    def map_index_duplicates(self, values, *args, on_device=False):
+        """map_index_duplicates(values[, mask], start_index) -> (left_indices, right_indices):
+        one pair per duplicate row of each left row's key, in left-row order, duplicates
+        ascending (hash_primitives.hpp:756-848).  Host int64 arrays; on_device=True: int64
+        DeviceArrays (the pairs never leave HBM)."""
+        rest = list(args)
+        mask = None
+        if rest and not isinstance(rest[0], (int, np.integer)):
+            mask = rest.pop(0)
+        start_index = int(rest.pop(0)) if rest else 0
+        values = self._keys(values)
+        device = isinstance(values, DeviceArray)
+        mkeep, mptr = _CounterBase._side(mask, device)
+        n_out = ctypes.c_uint64(0)
+        kptr = values.ptr if device else values.ctypes.data
+        # the pairs are counted and kept in the library, then read with a second call
+        _lib.call("vh_index_map_index_duplicates", self._handle, kptr, mptr, len(values), start_index,
+                  _lib.LOC_DEVICE if device else _lib.LOC_HOST, ctypes.byref(n_out), None, None)
+        if on_device:
+            left, right = DeviceArray(n_out.value, np.int64), DeviceArray(n_out.value, np.int64)
+            lptr, rptr = left.ptr, right.ptr
+        else:
+            left, right = np.empty(n_out.value, np.int64), np.empty(n_out.value, np.int64)
+            lptr, rptr = left.ctypes.data, right.ctypes.data
+        _lib.call("vh_index_map_index_duplicates", self._handle, None, None, 0, 0, _lib.LOC_HOST, ctypes.byref(n_out),
+                  lptr, rptr)
+        return left, right
+
+    def __sizeof__(self):
+        return len(self) * 16
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h:
+            try:
+                _lib.call("vh_index_destroy", h)
+            except Exception:
+                pass
+            self._handle = None
+
+
+def take_device(columns, indices, with_mask=False):
+    """Device gather (vh_take): ``[c[indices] for c in columns]`` for DeviceArray columns and a
+    DeviceArray of int32 / int64 indices; a negative index gives 0.  Eight columns share one
+    pass over the indices.  with_mask: also the DeviceArray of ``indices < 0`` (uint8)."""
+    n = len(indices)
+    if np.dtype(indices.dtype) not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise TypeError("take: indices must be int32 or int64")
+    outs = [DeviceArray(n, c.dtype) for c in columns]
+    mask = DeviceArray(n, np.uint8) if with_mask else None
+    k = len(columns)
+    dsts = (ctypes.c_void_p * max(k, 1))(*[o.ptr for o in outs])
+    srcs = (ctypes.c_void_p * max(k, 1))(*[c.ptr for c in columns])
+    isz = (ctypes.c_int * max(k, 1))(*[c.dtype.itemsize for c in columns])
+    _lib.call("vh_take", k, dsts, srcs, isz, indices.ptr, indices.dtype.itemsize, n, mask.ptr if with_mask else None)
+    return (outs, mask) if with_mask else outs
+
+
+def index_matched(lookup):
+    """The inner join's compaction (vh_index_matched): for a DeviceArray lookup, the positions
+    with ``lookup >= 0`` (int64 DeviceArray) and the lookup entries there."""
+    n = len(lookup)
+    rows = DeviceArray(n, np.int64)
+    out = DeviceArray(n, lookup.dtype)
+    m = ctypes.c_uint64(0)
+    _lib.call("vh_index_matched", lookup.ptr, lookup.dtype.itemsize, n, ctypes.byref(m), rows.ptr, out.ptr)
+    return rows[:m.value], out[:m.value]
+
+
 def _register():
     ns = globals()
     for dtype in DTYPES:
+        name = "index_hash_" + dtype
+        ns[name] = type(name, (_IndexHashBase,), {"_dtype": dtype, "__module__": __name__})
         name = "ordered_set_" + dtype
         ns[name] = type(name, (_OrderedSetBase,), {"_dtype": dtype, "__module__": __name__})
         name = "counter_" + dtype
@@ -349,6 +546,14 @@ def counter_type_from_dtype(dtype, transient=True):
     dt = np.dtype(dtype)
     name = "int64" if dt.kind in "mM" else dt.newbyteorder("=").name
     return globals()["counter_" + name]
+
+
+def index_type_from_dtype(dtype, transient=True, prime_growth=False):
+    """vaex.hash.index_type_from_dtype for primitive dtypes (datetimes index as int64);
+    transient and prime_growth have no meaning for the one GPU table."""
+    dt = np.dtype(dtype)
+    name = "int64" if dt.kind in "mM" else dt.newbyteorder("=").name
+    return globals()["index_hash_" + name]
 
 
 def ordered_set_type_from_dtype(dtype):
