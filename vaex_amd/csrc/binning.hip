@@ -199,29 +199,9 @@ __global__ __launch_bounds__(256) void k_agg_lds(BinPlan p, AggDev a, uint64_t n
 // column (cells < 2^16 by the LDS bound), and each aggregator's pass reads that column.
 constexpr int CELL_U = 4;  // rows per thread per step, loads issued together
 
-// 8 consecutive rows of a column into registers: one 8- to 64-byte load when the column is
-// 8 * sizeof(T) aligned (one byte per lane per instruction made the small-grid passes
-// instruction-bound), else per row; `cnt` < 8 rows (the tail) load per row
+// rows per thread per step of the small-grid passes: one load_rows8 group (common.hpp)
 constexpr int RU = 8;
-template <typename T> __device__ __forceinline__ void load_rows8(const T *p, uint64_t j, uint32_t cnt, bool al, T (&out)[RU]) {
-    if (al && cnt == RU) {
-        if constexpr (sizeof(T) == 1) {
-            const uint2 v = *reinterpret_cast<const uint2 *>(p + j);
-            __builtin_memcpy(out, &v, 8);
-        } else {
-            uint4 v[sizeof(T) / 2];
-#pragma unroll
-            for (int k = 0; k < (int)sizeof(T) / 2; k++) v[k] = reinterpret_cast<const uint4 *>(p + j)[k];
-            __builtin_memcpy(out, v, sizeof(out));
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < RU; u++) out[u] = (uint32_t)u < cnt ? p[j + u] : T{};
-    }
-}
-__device__ __forceinline__ bool aligned_rows8(const void *p, int isz) {
-    return (reinterpret_cast<uintptr_t>(p) % (uintptr_t)(8 * isz)) == 0;
-}
+static_assert(RU == ROWS8, "load_rows8 takes 8 rows");
 
 template <int KIND_B, typename T>
 __global__ __launch_bounds__(256) void k_cells_dim(BinnerDev b, uint64_t n, uint16_t *cells, int first) {

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/vaexhip.h"
@@ -154,6 +155,49 @@ __device__ inline uint64_t block_reserve(uint32_t my, uint32_t *s_w, unsigned lo
     return base;
 }
 
+// 8 consecutive rows of a column into registers: one 8- to 64-byte load when the column is
+// 8 * sizeof(T) aligned (one byte per lane per instruction made the small-grid passes
+// instruction-bound), else per row; `cnt` < 8 rows (the tail) load per row.  store_rows8 is
+// the matching store.  The callers keep their own names for the 8 (RU, CT_RPT, IX_RPT).
+constexpr int ROWS8 = 8;
+template <typename T> __device__ __forceinline__ void load_rows8(const T *p, uint64_t j, uint32_t cnt, bool al, T (&out)[ROWS8]) {
+    if (al && cnt == ROWS8) {
+        if constexpr (sizeof(T) == 1) {
+            const uint2 v = *reinterpret_cast<const uint2 *>(p + j);
+            __builtin_memcpy(out, &v, 8);
+        } else {
+            uint4 v[sizeof(T) / 2];
+#pragma unroll
+            for (int k = 0; k < (int)sizeof(T) / 2; k++) v[k] = reinterpret_cast<const uint4 *>(p + j)[k];
+            __builtin_memcpy(out, v, sizeof(out));
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < ROWS8; u++) out[u] = (uint32_t)u < cnt ? p[j + u] : T{};
+    }
+}
+template <typename T> __device__ __forceinline__ void store_rows8(T *p, uint64_t j, uint32_t cnt, bool al, const T (&v)[ROWS8]) {
+    static_assert(sizeof(T) >= 4, "whole 16-byte stores");
+    if (al && cnt == ROWS8) {
+        uint4 w[sizeof(T) / 2];
+        __builtin_memcpy(w, v, sizeof(v));
+#pragma unroll
+        for (int k = 0; k < (int)sizeof(T) / 2; k++) reinterpret_cast<uint4 *>(p + j)[k] = w[k];
+    } else {
+#pragma unroll
+        for (int u = 0; u < ROWS8; u++)
+            if ((uint32_t)u < cnt) p[j + u] = v[u];
+    }
+}
+__device__ __forceinline__ bool aligned_to(const void *p, int bytes) {
+    return (reinterpret_cast<uintptr_t>(p) % (uintptr_t)bytes) == 0;
+}
+__device__ __forceinline__ bool aligned_rows8(const void *p, int isz) { return aligned_to(p, ROWS8 * isz); }
+
+// idx[i] = i
+template <typename T> __global__ __launch_bounds__(256) void k_iota(T *idx, uint64_t n) {
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) idx[i] = (T)i;
+}
 
 template <typename T> struct is_float_t { static constexpr bool value = false; };
 template <> struct is_float_t<double> { static constexpr bool value = true; };
@@ -303,6 +347,10 @@ struct DevBuf {
         if (b == 0) return;
         ptr = dev_alloc(b);
         bytes = b;
+    }
+    void swap(DevBuf &o) {
+        ptr = std::exchange(o.ptr, ptr);
+        bytes = std::exchange(o.bytes, bytes);
     }
     template <typename T> T *as() const { return reinterpret_cast<T *>(ptr); }
 };

@@ -55,6 +55,7 @@
 #include "common.hpp"
 #include "hashset.hpp"
 #include "lds_table.hpp"
+#include "slot_table.hpp"
 
 using namespace vh;
 
@@ -73,7 +74,7 @@ struct vh_counter {
     uint64_t initial_cap = 0;
     CtTable main, scratch;
     DevBuf ctr;
-    DevBuf stage_keys, stage_mask, stage_select, stage_counts;
+    HostStage stage;
     int64_t nan_count = 0, null_count = 0, special_count = 0;
 };
 
@@ -81,7 +82,8 @@ namespace vh {
 
 constexpr uint32_t CT_LT_LOG2 = 13;
 constexpr uint32_t CT_LT = 1u << CT_LT_LOG2;  // LDS slots: 64 KiB (<= 4-byte keys), 96 KiB (8-byte keys)
-constexpr int CT_RPT = 8;                     // consecutive rows per lane and step
+constexpr int CT_RPT = 8;                     // consecutive rows per lane and step: one load_rows8 group
+static_assert(CT_RPT == ROWS8, "load_rows8 takes 8 rows");
 constexpr int CT_LDS_PROBES = 16;
 constexpr uint64_t CT_SEG_ROWS = uint64_t(1) << 16;    // a workgroup looks at its LDS fill this often
 constexpr uint64_t CT_FLUSH_ROWS = uint64_t(1) << 20;  // most rows of a workgroup between two flushes
@@ -111,29 +113,6 @@ struct CtParams {
 __device__ inline void ct_insert(const CtDev &g, uint64_t kb, uint64_t cnt, uint32_t *wg_new) {
     set_claim(g.tab, g.cap_mask, g.max_probe, kb, wg_new, &g.ctr[K_OVERFLOW],
               [&](uint64_t *count) { atomicAdd((unsigned long long *)count, (unsigned long long)cnt); });
-}
-
-// 8 consecutive rows of a column into registers (binning.hip load_rows8): wide loads when the
-// address is 8 * sizeof(T) aligned and all 8 rows exist, else per row
-template <typename T>
-__device__ __forceinline__ void ct_load8(const T *p, uint64_t j, uint32_t cnt, bool al, T (&out)[CT_RPT]) {
-    if (al && cnt == CT_RPT) {
-        if constexpr (sizeof(T) == 1) {
-            const uint2 v = *reinterpret_cast<const uint2 *>(p + j);
-            __builtin_memcpy(out, &v, 8);
-        } else {
-            uint4 v[sizeof(T) / 2];
-#pragma unroll
-            for (int k = 0; k < (int)sizeof(T) / 2; k++) v[k] = reinterpret_cast<const uint4 *>(p + j)[k];
-            __builtin_memcpy(out, v, sizeof(out));
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < CT_RPT; u++) out[u] = (uint32_t)u < cnt ? p[j + u] : T{};
-    }
-}
-__device__ __forceinline__ bool ct_aligned8(const void *p, int isz) {
-    return (reinterpret_cast<uintptr_t>(p) % (uintptr_t)(8 * isz)) == 0;
 }
 
 template <typename KB> struct CtLds {
@@ -185,8 +164,8 @@ __global__ __launch_bounds__(ct_threads<kb_t<T>>()) void k_ct_count(CtParams p, 
     const T *keys = static_cast<const T *>(p.keys);
     // rows_per_wg and seg_rows are multiples of the step, so every lane's 8 rows start at a
     // multiple of 8: the columns' base addresses decide the alignment
-    const bool al = ct_aligned8(keys, sizeof(T)) && (!p.mask || ct_aligned8(p.mask, 1)) &&
-                    (!p.select || ct_aligned8(p.select, 1));
+    const bool al = aligned_rows8(keys, sizeof(T)) && (!p.mask || aligned_rows8(p.mask, 1)) &&
+                    (!p.select || aligned_rows8(p.select, 1));
     const uint64_t r0 = blockIdx.x * p.rows_per_wg, r1 = min(p.n, r0 + p.rows_per_wg);
     uint64_t since = 0;  // rows counted into LDS since the last flush
     for (uint64_t s0 = r0; s0 < r1; s0 += p.seg_rows) {
@@ -197,9 +176,9 @@ __global__ __launch_bounds__(ct_threads<kb_t<T>>()) void k_ct_count(CtParams p, 
             const uint32_t cnt = (uint32_t)min<uint64_t>(CT_RPT, s1 - j);
             T v[CT_RPT];
             uint8_t m[CT_RPT], sel[CT_RPT];
-            ct_load8<T>(keys, j, cnt, al, v);
-            if (p.mask) ct_load8<uint8_t>(p.mask, j, cnt, al, m);
-            if (p.select) ct_load8<uint8_t>(p.select, j, cnt, al, sel);
+            load_rows8<T>(keys, j, cnt, al, v);
+            if (p.mask) load_rows8<uint8_t>(p.mask, j, cnt, al, m);
+            if (p.select) load_rows8<uint8_t>(p.select, j, cnt, al, sel);
             KB pk = 0;
             uint32_t run = 0;  // the lane's current run of equal regular keys
 #pragma unroll
@@ -336,11 +315,6 @@ __global__ __launch_bounds__(256) void k_ct_merge(const uint64_t *src, uint64_t 
     if (threadIdx.x == 0 && s_new) atomicAdd((unsigned long long *)&g.ctr[K_NEW], (unsigned long long)s_new);
 }
 
-__global__ __launch_bounds__(256) void k_ct_clear(uint64_t *tab, uint64_t cap) {
-    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * 256)
-        reinterpret_cast<ulonglong2 *>(tab)[i] = make_ulonglong2(SET_EMPTY, 0);
-}
-
 // ---- finish ---------------------------------------------------------------------------------
 // key bits (zero-extended) <-> a u64 whose unsigned order is the key's numeric order; floats
 // by their bit pattern, so -0.0 sorts just before 0.0
@@ -375,37 +349,15 @@ template <typename T> __host__ __device__ inline uint64_t ct_unordered(uint64_t 
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_ct_compact(const uint64_t *tab, uint64_t cap, uint64_t *okey, uint64_t *cnt,
-                                                    uint64_t *ctr) {
-    __shared__ uint32_t s_w[4];
-    __shared__ unsigned long long s_base;
-    constexpr int R = 8;
-    const uint64_t tile = 256ull * R, step = (uint64_t)gridDim.x * tile;
-    for (uint64_t t0 = blockIdx.x * tile; t0 < cap; t0 += step) {
-        const uint64_t i0 = t0 + (uint64_t)threadIdx.x * R;
-        ulonglong2 e[R];
-        uint32_t occ = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            e[r] = i0 + r < cap ? reinterpret_cast<const ulonglong2 *>(tab)[i0 + r] : make_ulonglong2(SET_EMPTY, 0);
-            if (e[r].x != SET_EMPTY) occ |= 1u << r;
-        }
-        uint64_t j = block_reserve<256>((uint32_t)__popc(occ), s_w, &s_base,
-                                        reinterpret_cast<unsigned long long *>(&ctr[K_CURSOR]));
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            if (!((occ >> r) & 1)) continue;
-            okey[j] = ct_ordered<T>(e[r].x);
-            cnt[j] = e[r].y;
-            j++;
-        }
+// what the finish keeps of an occupied slot: the key's sortable form and its count
+template <typename T> struct CtCompact {
+    static constexpr bool WIDE = true;
+    uint64_t *okey, *cnt;
+    __device__ void operator()(uint64_t j, uint64_t, uint64_t kb, uint64_t count) const {
+        okey[j] = ct_ordered<T>(kb);
+        cnt[j] = count;
     }
-}
-
-__global__ __launch_bounds__(256) void k_ct_iota(uint64_t *idx, uint64_t n) {
-    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) idx[i] = i;
-}
+};
 
 // the answer: entry j of the (count-sorted, maybe reversed) list as a typed key and a count
 template <typename T>
@@ -432,8 +384,7 @@ __global__ __launch_bounds__(256) void k_ct_emit(const uint64_t *okey, const uin
 // ---- host -------------------------------------------------------------------------------------
 static void ct_clear(CtTable &t) {
     if (t.clean || !t.cap) return;
-    hipLaunchKernelGGL(k_ct_clear, dim3(blocks_for(t.cap, 256)), dim3(256), 0, stream(), t.buf.as<uint64_t>(), t.cap);
-    VH_HIP(hipGetLastError());
+    slots_fresh(t.buf, t.cap, SlotPayload::ZERO);
     t.clean = true;
     t.distinct = 0;
 }
@@ -453,20 +404,13 @@ static CtDev ct_dev(vh_counter *c, const CtTable &t, bool unbounded) {
     CtDev g;
     g.tab = t.buf.as<uint64_t>();
     g.cap_mask = t.cap - 1;
-    g.max_probe = unbounded ? t.cap : std::min<uint64_t>(t.cap - 1, SET_MAX_PROBE);
+    g.max_probe = unbounded ? t.cap : slots_max_probe(t.cap);
     g.limit = unbounded ? ~0ULL : t.cap / 4 * 3;
     g.ctr = c->ctr.as<uint64_t>();
     return g;
 }
 
 static void ct_zero_ctr(vh_counter *c) { VH_HIP(hipMemsetAsync(c->ctr.ptr, 0, 8 * K_N, stream())); }
-
-static std::vector<uint64_t> ct_read_ctr(vh_counter *c) {
-    std::vector<uint64_t> v(K_N);
-    VH_HIP(hipMemcpyAsync(v.data(), c->ctr.ptr, 8 * K_N, hipMemcpyDeviceToHost, stream()));
-    VH_HIP(hipStreamSynchronize(stream()));
-    return v;
-}
 
 // One chunk (device-resident) through `launch`, which counts it into the table it is given.
 // Transactional: see "Growth never double counts" at the top of the file.
@@ -481,7 +425,7 @@ template <typename F> static void ct_chunk(vh_counter *c, uint64_t want_cap, F &
         S.clean = false;
         launch(ct_dev(c, S, false));
         VH_HIP(hipGetLastError());
-        k = ct_read_ctr(c);
+        k = slots_read_ctr(c->ctr, K_N);
         if (k[K_BAD]) fail(VH_ERR_ARG, "counter add: negative count");
         if (!k[K_OVERFLOW]) break;
         ct_alloc(S, S.cap * 4);
@@ -490,8 +434,7 @@ template <typename F> static void ct_chunk(vh_counter *c, uint64_t want_cap, F &
     CtTable &M = c->main;
     if (M.distinct == 0) {
         // the counter's table holds nothing: the scratch table becomes it
-        std::swap(M.buf.ptr, S.buf.ptr);
-        std::swap(M.buf.bytes, S.buf.bytes);
+        M.buf.swap(S.buf);
         std::swap(M.cap, S.cap);
         std::swap(M.distinct, S.distinct);
         std::swap(M.clean, S.clean);
@@ -499,24 +442,13 @@ template <typename F> static void ct_chunk(vh_counter *c, uint64_t want_cap, F &
         const uint64_t need = M.distinct + S.distinct;
         uint64_t ncap = M.cap;
         while (ncap < 2 * need) ncap *= 2;
-        if (ncap != M.cap) {
-            CtTable N;  // allocated before anything changes: a failure leaves the counter as it was
-            ct_alloc(N, ncap);
-            N.clean = false;
-            hipLaunchKernelGGL(k_ct_merge, dim3(blocks_for(M.cap, 256)), dim3(256), 0, st, M.buf.as<uint64_t>(), M.cap,
-                               ct_dev(c, N, true));
-            VH_HIP(hipGetLastError());
-            VH_HIP(hipStreamSynchronize(st));
-            N.distinct = M.distinct;
-            std::swap(M.buf.ptr, N.buf.ptr);
-            std::swap(M.buf.bytes, N.buf.bytes);
-            M.cap = ncap;
-        }
+        // the new table is allocated before anything changes: a failure leaves the counter as it was
+        if (ncap != M.cap) slots_grow(M.buf, M.cap, ncap, SlotPayload::ZERO);
         ct_zero_ctr(c);
         hipLaunchKernelGGL(k_ct_merge, dim3(blocks_for(S.cap, 256)), dim3(256), 0, st, S.buf.as<uint64_t>(), S.cap,
                            ct_dev(c, M, true));
         VH_HIP(hipGetLastError());
-        const auto k2 = ct_read_ctr(c);
+        const auto k2 = slots_read_ctr(c->ctr, K_N);
         if (k2[K_OVERFLOW]) fail(VH_ERR_RUNTIME, "counter merge: table full (internal error)");
         M.distinct += k2[K_NEW];
         M.clean = false;
@@ -542,7 +474,7 @@ static uint64_t ct_size_from_sample(vh_counter *c, const T *keys, const uint8_t 
     hipLaunchKernelGGL(k_sample_stats<SampleSlotCounts>, dim3(blocks_for(S.cap, 256)), dim3(256), 0, stream(),
                        SampleSlotCounts{S.buf.as<uint64_t>()}, S.cap, c->ctr.as<unsigned long long>() + K_D);
     VH_HIP(hipGetLastError());
-    const auto k = ct_read_ctr(c);
+    const auto k = slots_read_ctr(c->ctr, K_N);
     const double d = (double)k[K_D], f1 = (double)k[K_F1], f2 = (double)k[K_F2];
     // Chao1; with no key seen twice every sampled key may be distinct: as many as the rows
     double est = f2 > 0 ? d + f1 * f1 / (2 * f2) : (f1 > 0 ? (double)n : d);
@@ -583,44 +515,18 @@ static void ct_count_chunk(vh_counter *c, const void *keys, const uint8_t *mask,
 static void ct_update(vh_counter *c, const void *keys, const uint8_t *mask, const uint8_t *select, const int64_t *counts,
                       uint64_t n, int loc) {
     loc = resolve_loc(keys, loc);
-    const int isz = dtype_itemsize(c->dtype);
-    const uint64_t CH = loc == VH_LOC_HOST ? (uint64_t(1) << 24) : std::max<uint64_t>(n, 1);
-    hipStream_t st = stream();
-    for (uint64_t r0 = 0; r0 < n; r0 += CH) {
-        const uint64_t len = std::min(CH, n - r0);
-        const void *dk = reinterpret_cast<const char *>(keys) + r0 * isz;
-        const uint8_t *dm = mask ? mask + r0 : nullptr;
-        const uint8_t *ds = select ? select + r0 : nullptr;
-        const int64_t *dc = counts ? counts + r0 : nullptr;
-        if (loc == VH_LOC_HOST) {
-            c->stage_keys.ensure(len * isz);
-            VH_HIP(hipMemcpyAsync(c->stage_keys.ptr, dk, len * isz, hipMemcpyHostToDevice, st));
-            dk = c->stage_keys.ptr;
-            if (mask) {
-                c->stage_mask.ensure(len);
-                VH_HIP(hipMemcpyAsync(c->stage_mask.ptr, dm, len, hipMemcpyHostToDevice, st));
-                dm = c->stage_mask.as<uint8_t>();
-            }
-            if (select) {
-                c->stage_select.ensure(len);
-                VH_HIP(hipMemcpyAsync(c->stage_select.ptr, ds, len, hipMemcpyHostToDevice, st));
-                ds = c->stage_select.as<uint8_t>();
-            }
-            if (counts) {
-                c->stage_counts.ensure(len * 8);
-                VH_HIP(hipMemcpyAsync(c->stage_counts.ptr, dc, len * 8, hipMemcpyHostToDevice, st));
-                dc = c->stage_counts.as<int64_t>();
-            }
-        }
-        if (counts) {
-            VH_DISPATCH_DTYPE(c->dtype, T, ct_chunk(c, std::max<uint64_t>(c->initial_cap, 16), [&](const CtDev &g) {
-                                  hipLaunchKernelGGL(k_ct_add<T>, dim3(blocks_for(len, 256)), dim3(256), 0, st,
-                                                     static_cast<const T *>(dk), dm, dc, len, g);
-                              }));
-        } else {
-            VH_DISPATCH_DTYPE(c->dtype, T, ct_count_chunk<T>(c, dk, dm, ds, len));
-        }
-    }
+    // host columns are staged per 16 Mi rows; device columns are one chunk
+    c->stage.chunks({keys, mask, select, counts}, dtype_itemsize(c->dtype), n, loc, uint64_t(1) << 24, std::max<uint64_t>(n, 1),
+                    [&](const HashCols &d, uint64_t len, uint64_t) {
+                        if (counts) {
+                            VH_DISPATCH_DTYPE(c->dtype, T, ct_chunk(c, std::max<uint64_t>(c->initial_cap, 16), [&](const CtDev &g) {
+                                                  hipLaunchKernelGGL(k_ct_add<T>, dim3(blocks_for(len, 256)), dim3(256), 0, stream(),
+                                                                     static_cast<const T *>(d.keys), d.mask, d.counts, len, g);
+                                              }));
+                        } else {
+                            VH_DISPATCH_DTYPE(c->dtype, T, ct_count_chunk<T>(c, d.keys, d.mask, d.select, len));
+                        }
+                    });
 }
 
 template <typename T>
@@ -645,9 +551,7 @@ static void ct_read(vh_counter *c, int order, bool dropnan, bool dropmissing, vo
     // 1. compact the occupied slots, 2. append the special key
     ct_zero_ctr(c);
     if (M.distinct) {
-        hipLaunchKernelGGL(k_ct_compact<T>, dim3(blocks_for((M.cap + 7) / 8, 256)), dim3(256), 0, st, M.buf.as<uint64_t>(),
-                           M.cap, ck.as<uint64_t>(), cc.as<uint64_t>(), c->ctr.as<uint64_t>());
-        VH_HIP(hipGetLastError());
+        slots_compact(M.buf, M.cap, c->ctr.as<uint64_t>() + K_CURSOR, CtCompact<T>{ck.as<uint64_t>(), cc.as<uint64_t>()});
     }
     uint64_t head[4] = {0, 0, 0, 0};  // outlives the asynchronous copies below (synchronised before return)
     if (has_special) {
@@ -680,7 +584,7 @@ static void ct_read(vh_counter *c, int order, bool dropnan, bool dropmissing, vo
         idx.ensure(N * 8);
         scnt.ensure(N * 8);
         sidx.ensure(N * 8);
-        hipLaunchKernelGGL(k_ct_iota, dim3(blocks_for(N, 256)), dim3(256), 0, st, idx.as<uint64_t>(), N);
+        hipLaunchKernelGGL(k_iota<uint64_t>, dim3(blocks_for(N, 256)), dim3(256), 0, st, idx.as<uint64_t>(), N);
         VH_HIP(hipGetLastError());
         size_t tb = 0;
         VH_HIP(rocprim::radix_sort_pairs(nullptr, tb, lc.as<uint64_t>(), scnt.as<uint64_t>(), idx.as<uint64_t>(),
@@ -701,7 +605,7 @@ static void ct_read(vh_counter *c, int order, bool dropnan, bool dropmissing, vo
     VH_HIP(hipGetLastError());
     VH_HIP(hipMemcpyAsync(keys_out, okeys.ptr, N * sizeof(T), hipMemcpyDeviceToHost, st));
     VH_HIP(hipMemcpyAsync(counts_out, ocnt.ptr, N * 8, hipMemcpyDeviceToHost, st));
-    const auto k = ct_read_ctr(c);
+    const auto k = slots_read_ctr(c->ctr, K_N);
     if (has_null) *null_index = (int64_t)k[K_NULL_INDEX];
 }
 

@@ -1359,10 +1359,6 @@ __global__ __launch_bounds__(256) void k_ha_set_rank(const int64_t *okey, uint64
     }
 }
 
-__global__ __launch_bounds__(256) void k_ha_iota(uint32_t *idx, uint64_t m) {
-    for (uint64_t j = blockIdx.x * 256ull + threadIdx.x; j < m; j += (uint64_t)gridDim.x * 256) idx[j] = (uint32_t)j;
-}
-
 // result columns (key | count | sum[nv] | nonnull[nv], m each) permuted by order
 __global__ __launch_bounds__(256) void k_ha_permute(const int64_t *src, int64_t *dst, uint64_t m, int ncols,
                                                     const uint32_t *order) {
@@ -1642,8 +1638,7 @@ static void ensure_table(vh_hashagg *h, uint64_t need) {
                            h->slots, dst);
     });
     VH_HIP(hipGetLastError());
-    std::swap(h->tab.ptr, nt.ptr);
-    std::swap(h->tab.bytes, nt.bytes);
+    h->tab.swap(nt);
     h->slots = want;
 }
 
@@ -2352,7 +2347,7 @@ int vh_hashagg_order_first(vh_hashagg *h, const void *keys, uint64_t n, int loc)
         VH_HIP(hipGetLastError());
     }
     // order the groups by first row (or ordinal), then permute every result column
-    hipLaunchKernelGGL(k_ha_iota, dim3(blocks_for(m, 256, 8)), dim3(256), 0, st, idx, m);
+    hipLaunchKernelGGL(k_iota<uint32_t>, dim3(blocks_for(m, 256, 8)), dim3(256), 0, st, idx, m);
     VH_HIP(hipGetLastError());
     size_t tb = tmp_bytes;
     VH_HIP(rocprim::radix_sort_pairs(tmp, tb, first, rank2, idx, idx2, (size_t)m, 0, 64, st));
@@ -2571,11 +2566,6 @@ namespace vh {
 // ---- dense rank of int64 keys: (key, row) pairs radix-sorted, run heads flagged, an
 // inclusive scan of the flags numbers the runs, each sorted row scatters its run number
 // to its original row and every run head writes its key to the distinct list.
-__global__ void k_dr_iota(uint32_t *idx, uint64_t n) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        idx[i] = (uint32_t)i;
-}
-
 __global__ void k_dr_heads(const int64_t *sk, uint32_t *flag, uint64_t n) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
         flag[i] = (i == 0 || sk[i] != sk[i - 1]) ? 1u : 0u;
@@ -2738,7 +2728,7 @@ int vh_dense_rank_i64(uint64_t n, const int64_t *keys, int32_t *rank, int64_t *d
                                    rocprim::plus<uint32_t>(), st));
     tmp.ensure(std::max<size_t>(std::max(t1, t2), 16));
     const unsigned g = blocks_for(n, 256, 8);
-    hipLaunchKernelGGL(k_dr_iota, dim3(g), dim3(256), 0, st, idx.as<uint32_t>(), n);
+    hipLaunchKernelGGL(k_iota<uint32_t>, dim3(g), dim3(256), 0, st, idx.as<uint32_t>(), n);
     size_t tb = tmp.bytes;
     if (unsigned_sort)
         VH_HIP(rocprim::radix_sort_pairs(tmp.ptr, tb, reinterpret_cast<const uint64_t *>(keys), sk.as<uint64_t>(),
@@ -2893,8 +2883,7 @@ static uint64_t xo_fold(vh_hashagg *h, const uint64_t *rows, uint64_t M) {
                        scan.as<uint32_t>(), M, h->nv, h->vfloat, (uint64_t)mo, out.as<uint64_t>());
     VH_HIP(hipGetLastError());
     VH_HIP(hipStreamSynchronize(st));
-    std::swap(h->xres.ptr, out.ptr);
-    std::swap(h->xres.bytes, out.bytes);
+    h->xres.swap(out);
     h->res = h->xres.as<char>();
     return mo;
 }
@@ -2979,7 +2968,7 @@ int vh_hashagg_exchange(vh_hashagg *h, vh_comm *c, int gather) {
         if (mine) {
             DevBuf iota;
             iota.ensure(4 * mine);
-            hipLaunchKernelGGL(k_dr_iota, dim3(blocks_for(mine, 256, 8)), dim3(256), 0, st, iota.as<uint32_t>(), mine);
+            hipLaunchKernelGGL(k_iota<uint32_t>, dim3(blocks_for(mine, 256, 8)), dim3(256), 0, st, iota.as<uint32_t>(), mine);
             hipLaunchKernelGGL(k_xo_pack, dim3(blocks_for(mine, 256, 8)), dim3(256), 0, st, h->res, mine, h->nv,
                                iota.as<uint32_t>(), mrows.as<uint64_t>());
             VH_HIP(hipStreamSynchronize(st));

@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "hashset.hpp"
 #include "lds_table.hpp"
+#include "slot_table.hpp"
 
 using namespace vh;
 
@@ -43,7 +44,7 @@ struct vh_set {
     int dtype = VH_I64;
     uint64_t cap = 0;
     DevBuf tab, lut, ctr;
-    DevBuf stage_keys, stage_mask, stage_select;
+    HostStage stage;
     DevBuf c_slot, c_first, c_ord, c_bits;
     uint64_t rows_seen = 0;
     uint64_t nan_count_before = 0, null_count_before = 0;  // counters before the current chunk
@@ -674,52 +675,16 @@ __global__ __launch_bounds__(SB_THREADS) void k_si_direct(SiParams sp, SiTable g
     si_new_flush(&s_new, g.ctr);
 }
 
-__global__ void k_set_rehash(const uint64_t *otab, uint64_t ocap, uint64_t *ntab, uint64_t ncap_mask) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < ocap;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t kb = otab[2 * i];
-        if (kb == SET_EMPTY) continue;
-        uint64_t pos = hash64(kb) & ncap_mask;
-        for (;;) {
-            uint64_t old = atomicCAS((unsigned long long *)&ntab[2 * pos], (unsigned long long)SET_EMPTY,
-                                     (unsigned long long)kb);
-            if (old == SET_EMPTY) break;
-            pos = (pos + 1) & ncap_mask;
-        }
-        ntab[2 * pos + 1] = otab[2 * i + 1];
+// what the seal keeps of an occupied slot: its position, first row and key bits
+struct SetCompact {
+    static constexpr bool WIDE = false;
+    uint64_t *slot, *first, *bits;
+    __device__ void operator()(uint64_t j, uint64_t i, uint64_t kb, uint64_t row) const {
+        slot[j] = i;
+        first[j] = row;
+        bits[j] = kb;
     }
-}
-
-__global__ __launch_bounds__(256) void k_set_compact(const uint64_t *tab, uint64_t cap, uint64_t *slot, uint64_t *first,
-                                                     uint64_t *bits, uint64_t *ctr) {
-    // 8 consecutive slots per thread; output positions reserved once per workgroup and tile
-    // (one cursor add per wave was one same-address atomic per 64 slots)
-    __shared__ uint32_t s_w[4];
-    __shared__ unsigned long long s_base;
-    constexpr int R = 8;
-    const uint64_t tile = 256ull * R, step = (uint64_t)gridDim.x * tile;
-    for (uint64_t t0 = blockIdx.x * tile; t0 < cap; t0 += step) {
-        const uint64_t i0 = t0 + (uint64_t)threadIdx.x * R;
-        uint64_t kb[R];
-        uint32_t occ = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            kb[r] = i0 + r < cap ? tab[2 * (i0 + r)] : SET_EMPTY;
-            if (kb[r] != SET_EMPTY) occ |= 1u << r;
-        }
-        uint64_t j = block_reserve<256>((uint32_t)__popc(occ), s_w, &s_base,
-                                        reinterpret_cast<unsigned long long *>(&ctr[C_CURSOR]));
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            if (!((occ >> r) & 1)) continue;
-            const uint64_t i = i0 + r;
-            slot[j] = i;
-            first[j] = tab[2 * i + 1];
-            bits[j] = kb[r];
-            j++;
-        }
-    }
-}
+};
 
 // ---- first-appearance ranks without a sort: first rows are distinct, so the rank of key j
 // is the number of set bits below first[j] in a row bitmap (per-word popcounts + scan)
@@ -852,32 +817,9 @@ __global__ __launch_bounds__(256) void k_set_map_ordinal(const T *keys, uint64_t
     }
 }
 
-static void set_grow(vh_set *s, uint64_t new_cap) {
-    DevBuf nt;
-    nt.ensure(new_cap * 16);
-    VH_HIP(hipMemsetAsync(nt.ptr, 0xff, new_cap * 16, stream()));
-    if (s->cap) {
-        hipLaunchKernelGGL(k_set_rehash, dim3(blocks_for(s->cap, 256)), dim3(256), 0, stream(), s->tab.as<uint64_t>(),
-                           s->cap, nt.as<uint64_t>(), new_cap - 1);
-        VH_HIP(hipGetLastError());
-    }
-    VH_HIP(hipStreamSynchronize(stream()));
-    std::swap(s->tab.ptr, nt.ptr);
-    std::swap(s->tab.bytes, nt.bytes);
-    s->cap = new_cap;
-    s->sealed = false;
-}
-
-static std::vector<uint64_t> read_ctr(vh_set *s) {
-    std::vector<uint64_t> c(C_N);
-    VH_HIP(hipMemcpyAsync(c.data(), s->ctr.ptr, 8 * C_N, hipMemcpyDeviceToHost, stream()));
-    VH_HIP(hipStreamSynchronize(stream()));
-    return c;
-}
-
 static void set_seal(vh_set *s) {
     if (s->sealed) return;
-    auto c = read_ctr(s);
+    auto c = slots_read_ctr(s->ctr, C_N);
     const uint64_t cap = s->cap;
     s->c_slot.ensure(cap * 8);
     s->c_first.ensure(cap * 8);
@@ -885,11 +827,9 @@ static void set_seal(vh_set *s) {
     s->c_ord.ensure(cap * 8);
     uint64_t zero = 0;
     VH_HIP(hipMemcpyAsync(s->ctr.as<uint64_t>() + C_CURSOR, &zero, 8, hipMemcpyHostToDevice, stream()));
-    hipLaunchKernelGGL(k_set_compact, dim3(blocks_for((cap + 7) / 8, 256)), dim3(256), 0, stream(), s->tab.as<uint64_t>(), cap,
-                       s->c_slot.as<uint64_t>(), s->c_first.as<uint64_t>(), s->c_bits.as<uint64_t>(),
-                       s->ctr.as<uint64_t>());
-    VH_HIP(hipGetLastError());
-    c = read_ctr(s);
+    slots_compact(s->tab, cap, s->ctr.as<uint64_t>() + C_CURSOR,
+                  SetCompact{s->c_slot.as<uint64_t>(), s->c_first.as<uint64_t>(), s->c_bits.as<uint64_t>()});
+    c = slots_read_ctr(s->ctr, C_N);
     const uint64_t m = c[C_CURSOR];
     // special keys (at most 3), ordered by (sort key, tie) as the reference flushes them
     struct Spec {
@@ -1015,7 +955,7 @@ int vh_set_create(int dtype, vh_set **out) {
     std::vector<uint64_t> init(C_N, 0);
     init[C_NAN_FIRST] = init[C_NULL_FIRST] = init[C_SPECIAL_FIRST] = ~0ULL;
     VH_HIP(hipMemcpyAsync(s->ctr.ptr, init.data(), 8 * C_N, hipMemcpyHostToDevice, stream()));
-    set_grow(s.get(), 1 << 16);
+    slots_grow(s->tab, s->cap, 1 << 16);
     *out = s.release();
     VH_API_END
 }
@@ -1073,17 +1013,16 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
                            SampleCounts{smp.scnt}, sslots, smp.stats);
         VH_HIP(hipGetLastError());
     }
-    std::vector<uint64_t> fh(FINE + 3), c(C_N);
+    std::vector<uint64_t> fh(FINE + 3);
     VH_HIP(hipMemcpyAsync(fh.data(), smp.fine, 8 * (FINE + 3), hipMemcpyDeviceToHost, st));
-    VH_HIP(hipMemcpyAsync(c.data(), s->ctr.ptr, 8 * C_N, hipMemcpyDeviceToHost, st));
-    VH_HIP(hipStreamSynchronize(st));
+    std::vector<uint64_t> c = slots_read_ctr(s->ctr, C_N);
     const uint64_t sampled = hash_sampled_rows(fh.data());
     // a sample whose blocks covered every batch is taken as exact; at least one key
     const double dest = hash_estimate_keys(sampled, (double)fh[FINE], (double)fh[FINE + 1], (double)fh[FINE + 2], n,
                                            /*whole_chunk=*/sg.sblocks == sg.nbatch, /*at_least_one=*/true);
     // the HBM table at <= 1/2 load for what it holds plus the estimate
     const uint64_t need = c[C_DISTINCT] + (uint64_t)dest;
-    if (2 * need > s->cap) set_grow(s, next_pow2(2 * need));
+    if (2 * need > s->cap) slots_grow(s->tab, s->cap, next_pow2(2 * need));
     const uint32_t p_log2 = hash_p_log2(dest, SI_TARGET_KEYS, SI_MAX_P_LOG2);
     sp.p_log2 = p_log2;
     sp.P = 1u << p_log2;
@@ -1218,16 +1157,15 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
                 VH_HIP(hipGetLastError());
             }
         }
-        VH_HIP(hipMemcpyAsync(c.data(), s->ctr.ptr, 8 * C_N, hipMemcpyDeviceToHost, st));
-        VH_HIP(hipStreamSynchronize(st));
+        c = slots_read_ctr(s->ctr, C_N);
         if (!c[C_OVERFLOW]) {
-            if (c[C_DISTINCT] * 2 > s->cap) set_grow(s, next_pow2(c[C_DISTINCT] * 2));
+            if (c[C_DISTINCT] * 2 > s->cap) slots_grow(s->tab, s->cap, next_pow2(c[C_DISTINCT] * 2));
             break;
         }
         // the estimate missed: grow x4 and re-run the chunk (inserts are idempotent; the
         // special rows' counts of this chunk are taken back first)
         if (attempt > 16) fail(VH_ERR_RUNTIME, "hash set could not grow enough");
-        set_grow(s, s->cap * 4);
+        slots_grow(s->tab, s->cap, s->cap * 4);
         uint64_t reset[C_N];
         memcpy(reset, c.data(), sizeof(reset));
         reset[C_OVERFLOW] = 0;
@@ -1242,49 +1180,23 @@ static void si_chunk(vh_set *s, SiScratch &S, const void *keys, const uint8_t *m
 
 static void set_update(vh_set *s, const void *keys, const uint8_t *mask, const uint8_t *select, uint64_t n, int loc) {
     loc = resolve_loc(keys, loc);
-    const int isz = dtype_itemsize(s->dtype);
-    // host keys are staged per 16 Mi rows; device keys are taken 2^30 rows at a time (the
-    // pass-A regions of a chunk are ~8 B per row; each chunk merges every key once per unit)
-    const uint64_t CH = loc == VH_LOC_HOST ? (uint64_t(1) << 24) : (uint64_t(1) << 30);
+    s->sealed = false;  // whatever happens below (the table may grow before a chunk fails)
     SiScratch &S = si_scratch();
     std::lock_guard<std::mutex> lk(S.mu);
-    for (uint64_t r0 = 0; r0 < n; r0 += CH) {
-        const uint64_t len = std::min(CH, n - r0);
-        const void *dk = reinterpret_cast<const char *>(keys) + r0 * isz;
-        const uint8_t *dm = mask ? mask + r0 : nullptr;
-        const uint8_t *ds = select ? select + r0 : nullptr;
-        if (loc == VH_LOC_HOST) {
-            s->stage_keys.ensure(len * isz);
-            VH_HIP(hipMemcpyAsync(s->stage_keys.ptr, dk, len * isz, hipMemcpyHostToDevice, stream()));
-            dk = s->stage_keys.ptr;
-            if (mask) {
-                s->stage_mask.ensure(len);
-                VH_HIP(hipMemcpyAsync(s->stage_mask.ptr, dm, len, hipMemcpyHostToDevice, stream()));
-                dm = s->stage_mask.as<uint8_t>();
-            }
-            if (select) {
-                s->stage_select.ensure(len);
-                VH_HIP(hipMemcpyAsync(s->stage_select.ptr, ds, len, hipMemcpyHostToDevice, stream()));
-                ds = s->stage_select.as<uint8_t>();
-            }
-        }
-        // the chunk's NaN / null counts, restored if the chunk must be re-run
-        {
-            std::vector<uint64_t> c(C_N);
-            VH_HIP(hipMemcpyAsync(c.data(), s->ctr.ptr, 8 * C_N, hipMemcpyDeviceToHost, stream()));
-            VH_HIP(hipStreamSynchronize(stream()));
-            s->nan_count_before = c[C_NAN_COUNT];
-            s->null_count_before = c[C_NULL_COUNT];
-        }
-        si_chunk(s, S, dk, dm, ds, len, s->rows_seen + r0);
-    }
+    // host keys are staged per 16 Mi rows; device keys are taken 2^30 rows at a time (the
+    // pass-A regions of a chunk are ~8 B per row; each chunk merges every key once per unit)
+    s->stage.chunks({keys, mask, select, nullptr}, dtype_itemsize(s->dtype), n, loc, uint64_t(1) << 24, uint64_t(1) << 30,
+                    [&](const HashCols &d, uint64_t len, uint64_t r0) {
+                        // the chunk's NaN / null counts, restored if the chunk must be re-run
+                        const auto c = slots_read_ctr(s->ctr, C_N);
+                        s->nan_count_before = c[C_NAN_COUNT];
+                        s->null_count_before = c[C_NULL_COUNT];
+                        si_chunk(s, S, d.keys, d.mask, d.select, len, s->rows_seen + r0);
+                    });
     s->rows_seen += n;
-    {
-        auto c = read_ctr(s);
-        if (c[C_NAN_FIRST] != ~0ULL && s->nan_pos == ~0ULL) s->nan_pos = s->rows_seen;
-        if (c[C_NULL_FIRST] != ~0ULL && s->null_pos == ~0ULL) s->null_pos = s->rows_seen;
-    }
-    s->sealed = false;
+    const auto c = slots_read_ctr(s->ctr, C_N);
+    if (c[C_NAN_FIRST] != ~0ULL && s->nan_pos == ~0ULL) s->nan_pos = s->rows_seen;
+    if (c[C_NULL_FIRST] != ~0ULL && s->null_pos == ~0ULL) s->null_pos = s->rows_seen;
 }
 
 int vh_set_update(vh_set *s, const void *keys, const uint8_t *mask, uint64_t n, int loc) {
@@ -1342,11 +1254,7 @@ int vh_set_map_ordinal(vh_set *s, const void *keys, uint64_t n, int loc, void *o
     DevBuf dkeys, dout;
     const void *dk = keys;
     void *dout_p = out;
-    if (loc == VH_LOC_HOST && n) {
-        dkeys.ensure(n * isz);
-        VH_HIP(hipMemcpyAsync(dkeys.ptr, keys, n * isz, hipMemcpyHostToDevice, stream()));
-        dk = dkeys.ptr;
-    }
+    if (loc == VH_LOC_HOST && n) dk = HostStage::copy(dkeys, keys, n * isz);
     if (out_loc == VH_LOC_HOST && n) {
         dout.ensure(n * out_itemsize);
         dout_p = dout.ptr;

@@ -1,7 +1,11 @@
-// GPU open-address hash set shared by hashset.hip (ordered_set) and the
-// fused set-ordinal binner in binning.hip; also what the hash engines (hashset.hip,
-// hashagg.hip, counter.hip) share in HBM: the slot claim of a {key, payload} table and the
-// key sample.  Their LDS table is lds_table.hpp, their host plan hash_plan.hpp.
+// The open-address hash table in HBM, device side: hash64, key_bits, the slot claim of a 16-byte
+// {key, payload} table (set_claim: hashset.hip's ordered_set, counter.hip's hash counter,
+// index.hip's join index; hashagg.hip's struct-of-arrays table has a claim of its own), the key
+// sample of hashagg.hip, hashset.hip and counter.hip, and the sealed lookup table (SetDev) that
+// hashset.hip and index.hip build and that the fused set-ordinal binner of binning.hip, the
+// tile path (tiled.hip), hashagg.hip's set rank and index.hip's probe read.  The table's host
+// side (fresh table, growth, compaction, counter words, host staging) is slot_table.hpp, the
+// engines' LDS table lds_table.hpp, their host plan hash_plan.hpp.
 //
 // Layout in HBM: `tab[cap]` of 16-byte slots {key bits zero-extended (EMPTY = ~0),
 // first row the key was seen at (the ordinal order)}, so an insert probe and its

@@ -51,6 +51,7 @@
 #include "common.hpp"
 #include "hashset.hpp"
 #include "lds_table.hpp"
+#include "slot_table.hpp"
 
 using namespace vh;
 
@@ -89,7 +90,8 @@ struct vh_index {
 
 namespace vh {
 
-constexpr int IX_RPT = 8;  // consecutive rows per lane and step (map_index, update reads one)
+constexpr int IX_RPT = 8;  // consecutive rows per lane and step (map_index, update reads one): one load_rows8 group
+static_assert(IX_RPT == ROWS8, "load_rows8 / store_rows8 take 8 rows");
 constexpr int IX_THREADS = 256;
 constexpr uint64_t IX_LDS_BYTES = uint64_t(1) << 16;  // the LDS image of a LUT: 8192 packed or 4096 16-byte slots
 constexpr uint64_t IX_MIN_HBM_CAP = uint64_t(1) << 16;
@@ -106,43 +108,6 @@ struct IxParams {
     uint32_t max_probe;
     uint64_t *ctr;
 };
-
-// 8 consecutive items into registers (counter.hip ct_load8): wide loads when the caller found
-// every column 8-item aligned and all 8 rows exist, else per row
-template <typename T>
-__device__ __forceinline__ void ix_load8(const T *p, uint64_t j, uint32_t cnt, bool al, T (&out)[IX_RPT]) {
-    if (al && cnt == IX_RPT) {
-        if constexpr (sizeof(T) == 1) {
-            const uint2 v = *reinterpret_cast<const uint2 *>(p + j);
-            __builtin_memcpy(out, &v, 8);
-        } else {
-            uint4 v[sizeof(T) / 2];
-#pragma unroll
-            for (int k = 0; k < (int)sizeof(T) / 2; k++) v[k] = reinterpret_cast<const uint4 *>(p + j)[k];
-            __builtin_memcpy(out, v, sizeof(out));
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < IX_RPT; u++) out[u] = (uint32_t)u < cnt ? p[j + u] : T{};
-    }
-}
-template <typename T>
-__device__ __forceinline__ void ix_store8(T *p, uint64_t j, uint32_t cnt, bool al, const T (&v)[IX_RPT]) {
-    static_assert(sizeof(T) >= 4, "lookup entries are int32 or int64");
-    if (al && cnt == IX_RPT) {
-        uint4 w[sizeof(T) / 2];
-        __builtin_memcpy(w, v, sizeof(v));
-#pragma unroll
-        for (int k = 0; k < (int)sizeof(T) / 2; k++) reinterpret_cast<uint4 *>(p + j)[k] = w[k];
-    } else {
-#pragma unroll
-        for (int u = 0; u < IX_RPT; u++)
-            if ((uint32_t)u < cnt) p[j + u] = v[u];
-    }
-}
-__device__ __forceinline__ bool ix_aligned(const void *p, int bytes) {
-    return (reinterpret_cast<uintptr_t>(p) % (uintptr_t)bytes) == 0;
-}
 
 // ---- update ---------------------------------------------------------------------------------
 template <typename T> __global__ __launch_bounds__(IX_THREADS) void k_ix_update(IxParams p) {
@@ -217,22 +182,6 @@ template <typename T> __global__ __launch_bounds__(IX_THREADS) void k_ix_update(
             atomicAdd(&c[X_SPEC_CNT], (unsigned long long)s_spec);
             atomicMin(&c[X_SPEC_FIRST], s_spec_first);
         }
-    }
-}
-
-// every occupied slot of the old table into the new, larger one (unbounded probing)
-__global__ __launch_bounds__(256) void k_ix_rehash(const uint64_t *otab, uint64_t ocap, uint64_t *ntab, uint64_t ncap_mask) {
-    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < ocap; i += (uint64_t)gridDim.x * 256) {
-        const ulonglong2 e = reinterpret_cast<const ulonglong2 *>(otab)[i];
-        if (e.x == SET_EMPTY) continue;
-        uint64_t pos = hash64(e.x) & ncap_mask;
-        for (;;) {
-            const uint64_t old = atomicCAS((unsigned long long *)&ntab[2 * pos], (unsigned long long)SET_EMPTY,
-                                           (unsigned long long)e.x);
-            if (old == SET_EMPTY) break;
-            pos = (pos + 1) & ncap_mask;
-        }
-        ntab[2 * pos + 1] = e.y;
     }
 }
 
@@ -318,7 +267,7 @@ __global__ __launch_bounds__(IX_THREADS) void k_ix_map(const T *keys, const uint
         }
     };
     // CONSEC: every lane's rows start at a multiple of 8: the base addresses decide the alignment
-    const bool al = ix_aligned(keys, 8 * sizeof(T)) && (!mask || ix_aligned(mask, 8)) && ix_aligned(out, 8 * sizeof(O));
+    const bool al = aligned_rows8(keys, sizeof(T)) && (!mask || aligned_rows8(mask, 1)) && aligned_rows8(out, sizeof(O));
     bool unk = false;
     const uint64_t tile = (uint64_t)IX_THREADS * R;
     for (uint64_t t0 = blockIdx.x * tile; t0 < n; t0 += (uint64_t)gridDim.x * tile) {
@@ -331,8 +280,8 @@ __global__ __launch_bounds__(IX_THREADS) void k_ix_map(const T *keys, const uint
             j = t0 + (uint64_t)threadIdx.x * R;
             if (j >= n) continue;
             cnt = (uint32_t)min<uint64_t>(R, n - j);
-            ix_load8<T>(keys, j, cnt, al, v);
-            if (mask) ix_load8<uint8_t>(mask, j, cnt, al, m);
+            load_rows8<T>(keys, j, cnt, al, v);
+            if (mask) load_rows8<uint8_t>(mask, j, cnt, al, m);
 #pragma unroll
             for (int r = 0; r < R; r++) ok[r] = (uint32_t)r < cnt;
         } else {
@@ -388,7 +337,7 @@ __global__ __launch_bounds__(IX_THREADS) void k_ix_map(const T *keys, const uint
             o[r] = (O)res;
         }
         if constexpr (CONSEC) {
-            if constexpr (R == IX_RPT) ix_store8<O>(out, j, cnt, al, o);
+            if constexpr (R == IX_RPT) store_rows8<O>(out, j, cnt, al, o);
         } else {
 #pragma unroll
             for (int r = 0; r < R; r++)
@@ -450,7 +399,7 @@ __device__ __forceinline__ void tk_column(V *dst, const V *src, uint64_t j, uint
     V val[TK_RPT];
 #pragma unroll
     for (int r = 0; r < TK_RPT; r++) val[r] = ((uint32_t)r < cnt && ix[r] >= 0) ? src[ix[r]] : V(0);
-    if (cnt == TK_RPT && ix_aligned(dst, TK_RPT * sizeof(V))) {
+    if (cnt == TK_RPT && aligned_to(dst, TK_RPT * sizeof(V))) {
         using W = std::conditional_t<sizeof(V) == 8, uint4, std::conditional_t<sizeof(V) == 4, uint4,
                   std::conditional_t<sizeof(V) == 2, uint2, uint32_t>>>;
         constexpr int NW = TK_RPT * sizeof(V) / sizeof(W);
@@ -467,7 +416,7 @@ __device__ __forceinline__ void tk_column(V *dst, const V *src, uint64_t j, uint
 
 template <typename I>
 __global__ __launch_bounds__(256) void k_take(TakeArgs a, const I *idx, uint64_t n, uint8_t *mask_out) {
-    const bool al = ix_aligned(idx, TK_RPT * sizeof(I));
+    const bool al = aligned_to(idx, TK_RPT * sizeof(I));
     const uint64_t tile = 256ull * TK_RPT;
     for (uint64_t t0 = blockIdx.x * tile; t0 < n; t0 += (uint64_t)gridDim.x * tile) {
         const uint64_t j = t0 + (uint64_t)threadIdx.x * TK_RPT;
@@ -520,23 +469,6 @@ __global__ __launch_bounds__(256) void k_matched_scatter(const I *idx, const uin
 }
 
 // ---- host -----------------------------------------------------------------------------------
-static uint32_t ix_max_probe(uint64_t cap) { return (uint32_t)std::min<uint64_t>(cap - 1, SET_MAX_PROBE); }
-
-static void ix_grow(vh_index *x, uint64_t new_cap) {
-    DevBuf nt;
-    nt.ensure(new_cap * 16);
-    VH_HIP(hipMemsetAsync(nt.ptr, 0xff, new_cap * 16, stream()));
-    if (x->cap) {
-        hipLaunchKernelGGL(k_ix_rehash, dim3(blocks_for(x->cap, 256)), dim3(256), 0, stream(), x->tab.as<uint64_t>(), x->cap,
-                           nt.as<uint64_t>(), new_cap - 1);
-        VH_HIP(hipGetLastError());
-    }
-    VH_HIP(hipStreamSynchronize(stream()));
-    std::swap(x->tab.ptr, nt.ptr);
-    std::swap(x->tab.bytes, nt.bytes);
-    x->cap = new_cap;
-}
-
 // one device-resident chunk into the table; `flags_in` (a retained chunk of another index)
 // replaces mask / select
 static void ix_chunk(vh_index *x, const void *keys, const uint8_t *mask, const uint8_t *select, const uint8_t *flags_in,
@@ -550,15 +482,15 @@ static void ix_chunk(vh_index *x, const void *keys, const uint8_t *mask, const u
         // 1e8 probes into a few hundred hot lines queue up (both routes took 1.0 ms at 4096 keys
         // in 8192 slots against 0.87 ms at 1e5 keys)
         if (want * (dtype_itemsize(x->dtype) > 4 ? 16 : 8) > IX_LDS_BYTES) want = std::max<uint64_t>(want, IX_MIN_HBM_CAP);
-        if (want > x->cap) ix_grow(x, want);
+        if (want > x->cap) slots_grow(x->tab, x->cap, want);
     }
-    uint64_t c[X_N];
+    std::vector<uint64_t> c;
     for (int attempt = 0;; attempt++) {
         uint64_t init[X_N] = {0};
         init[X_DISTINCT] = x->distinct;
         init[X_SPEC_FIRST] = ~0ULL;
         VH_HIP(hipMemcpyAsync(x->ctr.ptr, init, sizeof(init), hipMemcpyHostToDevice, st));
-        IxParams p{keys, mask, select, flags_in, flags_out, n, row0, x->tab.as<uint64_t>(), x->cap - 1, ix_max_probe(x->cap),
+        IxParams p{keys, mask, select, flags_in, flags_out, n, row0, x->tab.as<uint64_t>(), x->cap - 1, slots_max_probe(x->cap),
                    x->ctr.as<uint64_t>()};
         {
             TimedScope ts("index_update");
@@ -566,14 +498,13 @@ static void ix_chunk(vh_index *x, const void *keys, const uint8_t *mask, const u
                               hipLaunchKernelGGL(k_ix_update<T>, dim3(blocks_for(n, IX_THREADS)), dim3(IX_THREADS), 0, st, p));
             VH_HIP(hipGetLastError());
         }
-        VH_HIP(hipMemcpyAsync(c, x->ctr.ptr, sizeof(c), hipMemcpyDeviceToHost, st));
-        VH_HIP(hipStreamSynchronize(st));
+        c = slots_read_ctr(x->ctr, X_N);
         x->distinct = c[X_DISTINCT];  // a failed attempt's keys stay in the table
         if (!c[X_OVERFLOW]) break;
         if (attempt > 24) fail(VH_ERR_RUNTIME, "index_hash could not grow enough");
-        ix_grow(x, x->cap * 4);
+        slots_grow(x->tab, x->cap, x->cap * 4);
     }
-    if (x->distinct * 2 > x->cap) ix_grow(x, next_pow2(x->distinct * 2));
+    if (x->distinct * 2 > x->cap) slots_grow(x->tab, x->cap, next_pow2(x->distinct * 2));
     x->regular_rows += c[X_ROWS];
     x->special_rows += c[X_SPEC_CNT];
     if (c[X_SPEC_CNT]) x->special_first = x->special_first < 0 ? (int64_t)c[X_SPEC_FIRST]
@@ -595,7 +526,7 @@ static void ix_update(vh_index *x, const void *keys, const uint8_t *mask, const 
     const uint64_t CH = loc == VH_LOC_HOST ? (uint64_t(1) << 24) : n;
     hipStream_t st = stream();
     const hipMemcpyKind kind = loc == VH_LOC_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    DevBuf dmask, dselect;
+    HostStage stage;
     for (uint64_t r0 = 0; r0 < n; r0 += CH) {
         const uint64_t len = std::min(CH, n - r0);
         std::unique_ptr<IxChunk> ch(new IxChunk());
@@ -607,16 +538,10 @@ static void ix_update(vh_index *x, const void *keys, const uint8_t *mask, const 
         if (ch->has_flags) ch->flags.ensure(len);
         const uint8_t *dm = mask ? mask + r0 : nullptr, *ds = select ? select + r0 : nullptr;
         // mask / select are staged when they are host arrays, wherever the keys are
-        if (mask && (loc == VH_LOC_HOST || resolve_loc(mask, VH_LOC_AUTO) == VH_LOC_HOST)) {
-            dmask.ensure(len);
-            VH_HIP(hipMemcpyAsync(dmask.ptr, dm, len, hipMemcpyHostToDevice, st));
-            dm = dmask.as<uint8_t>();
-        }
-        if (select && (loc == VH_LOC_HOST || resolve_loc(select, VH_LOC_AUTO) == VH_LOC_HOST)) {
-            dselect.ensure(len);
-            VH_HIP(hipMemcpyAsync(dselect.ptr, ds, len, hipMemcpyHostToDevice, st));
-            ds = dselect.as<uint8_t>();
-        }
+        if (mask && (loc == VH_LOC_HOST || resolve_loc(mask, VH_LOC_AUTO) == VH_LOC_HOST))
+            dm = static_cast<const uint8_t *>(HostStage::copy(stage.mask, dm, len));
+        if (select && (loc == VH_LOC_HOST || resolve_loc(select, VH_LOC_AUTO) == VH_LOC_HOST))
+            ds = static_cast<const uint8_t *>(HostStage::copy(stage.select, ds, len));
         ix_chunk(x, ch->keys.ptr, dm, ds, nullptr, ch->has_flags ? ch->flags.as<uint8_t>() : nullptr, len, ch->row0);
         x->chunks.push_back(std::move(ch));
     }
@@ -651,7 +576,7 @@ static void ix_seal(vh_index *x) {
             VH_DISPATCH_DTYPE(x->dtype, T,
                               hipLaunchKernelGGL(k_ix_dup_keys<T>, dim3(blocks_for(ch->n, 256)), dim3(256), 0, st,
                                                  ch->keys.as<T>(), ch->has_flags ? ch->flags.as<uint8_t>() : nullptr, ch->n,
-                                                 ch->row0, x->tab.as<uint64_t>(), x->cap - 1, ix_max_probe(x->cap),
+                                                 ch->row0, x->tab.as<uint64_t>(), x->cap - 1, slots_max_probe(x->cap),
                                                  x->special_first, sentinel, skey.as<uint32_t>() + off,
                                                  srow.as<int64_t>() + off));
             VH_HIP(hipGetLastError());
@@ -699,26 +624,18 @@ static SetDev ix_view(vh_index *x) {
     return d;
 }
 
-// keys (and mask) of a probe call on the device: staged when they are host arrays
+// keys (and mask) of a probe call of n > 0 rows on the device: staged when they are host
+// arrays (a host mask also when the keys are on the device)
 struct IxProbeIn {
-    DevBuf dkeys, dmask;
+    HostStage stage;
     const void *keys;
     const uint8_t *mask;
 };
 static void ix_stage(vh_index *x, IxProbeIn &in, const void *keys, const uint8_t *mask, uint64_t n, int loc) {
-    const int isz = dtype_itemsize(x->dtype);
-    in.keys = keys;
+    in.keys = loc == VH_LOC_HOST ? HostStage::copy(in.stage.keys, keys, n * dtype_itemsize(x->dtype)) : keys;
     in.mask = mask;
-    if (loc == VH_LOC_HOST && n) {
-        in.dkeys.ensure(n * isz);
-        VH_HIP(hipMemcpyAsync(in.dkeys.ptr, keys, n * isz, hipMemcpyHostToDevice, stream()));
-        in.keys = in.dkeys.ptr;
-        if (mask) {
-            in.dmask.ensure(n);
-            VH_HIP(hipMemcpyAsync(in.dmask.ptr, mask, n, hipMemcpyHostToDevice, stream()));
-            in.mask = in.dmask.as<uint8_t>();
-        }
-    }
+    if (mask && (loc == VH_LOC_HOST || resolve_loc(mask, VH_LOC_AUTO) == VH_LOC_HOST))
+        in.mask = static_cast<const uint8_t *>(HostStage::copy(in.stage.mask, mask, n));
 }
 
 // The form per lookup table, from the A/B of DESIGN.md 5.18 (same process, 1e8 rows): the
@@ -751,7 +668,7 @@ int vh_index_create(int dtype, uint64_t initial_capacity, vh_index **out) {
     x->dtype = dtype;
     x->explicit_cap = initial_capacity != 0;
     x->ctr.ensure(8 * (X_N + 1));  // + the probe's unknown flag
-    ix_grow(x.get(), initial_capacity ? initial_capacity : IX_DEFAULT_CAP);
+    slots_grow(x->tab, x->cap, initial_capacity ? initial_capacity : IX_DEFAULT_CAP);
     *out = x.release();
     VH_API_END
 }
@@ -824,11 +741,6 @@ int vh_index_map_index(vh_index *x, const void *keys, const uint8_t *mask, uint6
     hipStream_t st = stream();
     IxProbeIn in;
     ix_stage(x, in, keys, mask, n, loc);
-    if (mask && loc != VH_LOC_HOST && resolve_loc(mask, VH_LOC_AUTO) == VH_LOC_HOST) {
-        in.dmask.ensure(n);
-        VH_HIP(hipMemcpyAsync(in.dmask.ptr, mask, n, hipMemcpyHostToDevice, st));
-        in.mask = in.dmask.as<uint8_t>();
-    }
     DevBuf dout;
     void *dout_p = out;
     if (out_loc == VH_LOC_HOST) {
@@ -885,11 +797,6 @@ int vh_index_map_index_duplicates(vh_index *x, const void *keys, const uint8_t *
     loc = resolve_loc(keys, loc);
     IxProbeIn in;
     ix_stage(x, in, keys, mask, n, loc);
-    if (mask && loc != VH_LOC_HOST && resolve_loc(mask, VH_LOC_AUTO) == VH_LOC_HOST) {
-        in.dmask.ensure(n);
-        VH_HIP(hipMemcpyAsync(in.dmask.ptr, mask, n, hipMemcpyHostToDevice, st));
-        in.mask = in.dmask.as<uint8_t>();
-    }
     DevBuf cnt, off, beg, tmp;
     cnt.ensure((n + 1) * 4);
     off.ensure((n + 1) * 8);
@@ -899,7 +806,7 @@ int vh_index_map_index_duplicates(vh_index *x, const void *keys, const uint8_t *
     VH_DISPATCH_DTYPE(x->dtype, T,
                       hipLaunchKernelGGL(k_ix_dup_count<T>, dim3(blocks_for(n, 256)), dim3(256), 0, st,
                                          static_cast<const T *>(in.keys), in.mask, n, x->tab.as<uint64_t>(), x->cap - 1,
-                                         ix_max_probe(x->cap), x->dup_begin.as<uint32_t>(), x->dup_count.as<uint32_t>(),
+                                         slots_max_probe(x->cap), x->dup_begin.as<uint32_t>(), x->dup_count.as<uint32_t>(),
                                          cnt.as<uint32_t>(), beg.as<uint32_t>()));
     VH_HIP(hipGetLastError());
     // off[i] = pairs before left row i, off[n] = all pairs

@@ -237,10 +237,8 @@ static void nu_reserve(vh_agg *a, uint64_t extra) {
         VH_HIP(hipMemcpyAsync(nv.ptr, a->nu_val.ptr, a->nu_n * 8, hipMemcpyDeviceToDevice, stream()));
     }
     VH_HIP(hipStreamSynchronize(stream()));
-    std::swap(a->nu_cell.ptr, nc.ptr);
-    std::swap(a->nu_cell.bytes, nc.bytes);
-    std::swap(a->nu_val.ptr, nv.ptr);
-    std::swap(a->nu_val.bytes, nv.bytes);
+    a->nu_cell.swap(nc);
+    a->nu_val.swap(nv);
 }
 
 // sort the list by (cell, value), count distinct pairs per cell into `distinct` (L

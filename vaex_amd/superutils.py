@@ -27,13 +27,82 @@ from .superagg import _column
 DTYPES = _lib.DTYPES
 
 
-class _OrderedSetBase:
+class _HashBase:
+    """What the three hash handles share: the C handle (``<prefix>_create`` / ``_destroy``),
+    ``<prefix>_info`` (length, nan_count, null_count, then the engine's own words), the
+    parsing of ``update(keys[, mask], ...)`` and where a mask / select column has to be."""
     _dtype = "int64"
+    _prefix = None    # vh_set / vh_counter / vh_index
+    _info_words = 5   # int64 words <prefix>_info writes
+
+    def _create(self, *args):
+        h = ctypes.c_void_p()
+        _lib.call(self._prefix + "_create", _lib.DTYPE_CODE[self._dtype], *args, ctypes.byref(h))
+        self._handle = h.value
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h:
+            try:
+                _lib.call(self._prefix + "_destroy", h)
+            except Exception:
+                pass
+            self._handle = None
+
+    def _info(self, *more):
+        vals = [ctypes.c_int64() for _ in range(self._info_words)]
+        _lib.call(self._prefix + "_info", self._handle, *[ctypes.byref(v) for v in vals], *more)
+        return [v.value for v in vals]
+
+    def __len__(self):
+        return self._info()[0]
+
+    def length(self):
+        return len(self)
+
+    def __sizeof__(self):
+        return len(self) * 16
+
+    nan_count = property(lambda self: self._info()[1])
+    null_count = property(lambda self: self._info()[2])
+    has_nan = property(lambda self: self._info()[1] > 0)
+    has_null = property(lambda self: self._info()[2] > 0)
+
+    @staticmethod
+    def _update_args(ar, args, kwargs):
+        """``(ar, *args, **kwargs)`` of an update call as (keys, mask, the other positional
+        arguments); a masked array gives its data and adds its mask.  Pops ``mask`` from kwargs."""
+        mask = None
+        rest = list(args)
+        if rest and (isinstance(rest[0], (np.ndarray, list, DeviceArray)) or rest[0] is None):
+            mask = rest.pop(0)
+        mask = kwargs.pop("mask", mask)
+        if np.ma.isMaskedArray(ar):
+            m = np.ma.getmaskarray(ar)
+            mask = m if mask is None else (np.asarray(mask, bool) | m)
+            ar = ar.data
+        return ar, mask, rest
+
+    @staticmethod
+    def _side(a, device):
+        """A mask / select column where the keys are: (object kept alive, pointer)."""
+        if a is None:
+            return None, None
+        if device:
+            if not isinstance(a, DeviceArray):
+                a = DeviceArray.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
+            return a, a.ptr
+        if isinstance(a, DeviceArray):
+            a = a.to_numpy()
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        return a, a.ctypes.data
+
+
+class _OrderedSetBase(_HashBase):
+    _prefix = "vh_set"
 
     def __init__(self, *args):
-        h = ctypes.c_void_p()
-        _lib.call("vh_set_create", _lib.DTYPE_CODE[self._dtype], ctypes.byref(h))
-        self._handle = h.value
+        self._create()
         self.fingerprint = ""
         self.sealed = False
         if len(args) >= 4:
@@ -58,19 +127,11 @@ class _OrderedSetBase:
     # ---- building --------------------------------------------------------------
     def update(self, ar, *args, **kwargs):
         """update(keys[, mask], start_index=0, chunk_size=..., bucket_size=..., return_values=False)"""
-        mask = None
-        rest = list(args)
-        if rest and (isinstance(rest[0], (np.ndarray, list, DeviceArray)) or rest[0] is None):
-            mask = rest.pop(0)
-        mask = kwargs.pop("mask", mask)
+        ar, mask, _ = self._update_args(ar, args, kwargs)
         # select (this build): only rows where select != 0 enter the set (a filtered or
         # selected chunk, evaluated on the device, without compacting it)
         select = kwargs.pop("select", None)
         return_values = kwargs.get("return_values", False)
-        if np.ma.isMaskedArray(ar):
-            m = np.ma.getmaskarray(ar)
-            mask = m if mask is None else (np.asarray(mask, bool) | m)
-            ar = ar.data
         if not isinstance(ar, DeviceArray):
             ar = np.ascontiguousarray(ar, dtype=self._dtype)
         kptr, n, _, _, loc, keep = _column(ar)
@@ -107,23 +168,8 @@ class _OrderedSetBase:
         self.sealed = True
 
     # ---- reading ---------------------------------------------------------------
-    def _info(self):
-        vals = [ctypes.c_int64() for _ in range(5)]
-        _lib.call("vh_set_info", self._handle, *[ctypes.byref(v) for v in vals])
-        return [v.value for v in vals]
-
-    def __len__(self):
-        return self._info()[0]
-
-    def length(self):
-        return len(self)
-
-    nan_count = property(lambda self: self._info()[1])
-    null_count = property(lambda self: self._info()[2])
     nan_value = property(lambda self: self._info()[3])
     null_value = property(lambda self: self._info()[4])
-    has_nan = property(lambda self: self._info()[1] > 0)
-    has_null = property(lambda self: self._info()[2] > 0)
 
     def key_array(self):
         n = len(self)
@@ -166,28 +212,16 @@ class _OrderedSetBase:
         out[:] = values  # one map: offsets are all 0 (hash_common::flatten_values)
         return out
 
-    def __sizeof__(self):
-        return len(self) * 16
-
     def __reduce__(self):
         keys = self.key_array()
         return (type(self), (keys, self.null_value, self.nan_count, self.null_count, self.fingerprint))
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h:
-            try:
-                _lib.call("vh_set_destroy", h)
-            except Exception:
-                pass
-            self._handle = None
 
 
 # slots of the LDS table a workgroup counts into (counter.hip CT_LT)
 COUNTER_LDS_SLOTS = 8192
 
 
-class _CounterBase:
+class _CounterBase(_HashBase):
     """``counter_<dtype>`` (``hash_primitives.hpp:328-415``; bindings ``hash_primitives.cpp``
     ``init_hash_``): key -> occurrence count over the GPU hash counter of libvaexhip.
 
@@ -196,14 +230,13 @@ class _CounterBase:
     (the reference's order is its hash maps' iteration order; value_counts sorts by count).
     ``counter_<t>(keys, counts, null_index)`` rebuilds one (``__reduce__``);
     ``counter_<t>(initial_capacity=16)`` starts the table at 16 slots."""
-    _dtype = "int64"
+    _prefix = "vh_counter"
+    _info_words = 3
 
     def __init__(self, *args, initial_capacity=0):
-        h = ctypes.c_void_p()
         if len(args) == 1 and isinstance(args[0], (int, np.integer)):
             args = ()  # counter(nmaps): one table on the GPU
-        _lib.call("vh_counter_create", _lib.DTYPE_CODE[self._dtype], int(initial_capacity), ctypes.byref(h))
-        self._handle = h.value
+        self._create(int(initial_capacity))
         if len(args) >= 2:
             keys, counts = args[:2]
             null_index = args[2] if len(args) > 2 else -1
@@ -217,16 +250,8 @@ class _CounterBase:
     # ---- building --------------------------------------------------------------
     def update(self, ar, *args, **kwargs):
         """update(keys[, mask], select=None): rows where select == 0 are not seen at all."""
-        mask = None
-        rest = list(args)
-        if rest and (isinstance(rest[0], (np.ndarray, list, DeviceArray)) or rest[0] is None):
-            mask = rest.pop(0)
-        mask = kwargs.pop("mask", mask)
+        ar, mask, _ = self._update_args(ar, args, kwargs)
         select = kwargs.pop("select", None)
-        if np.ma.isMaskedArray(ar):
-            m = np.ma.getmaskarray(ar)
-            mask = m if mask is None else (np.asarray(mask, bool) | m)
-            ar = ar.data
         if not isinstance(ar, DeviceArray):
             ar = np.ascontiguousarray(ar, dtype=self._dtype)
         device = isinstance(ar, DeviceArray)
@@ -237,20 +262,6 @@ class _CounterBase:
         skeep, sptr = self._side(select, device)
         if n:
             _lib.call("vh_counter_update", self._handle, kptr, mptr, sptr, n, loc)
-
-    @staticmethod
-    def _side(a, device):
-        """A mask / select column where the keys are: (object kept alive, pointer)."""
-        if a is None:
-            return None, None
-        if device:
-            if not isinstance(a, DeviceArray):
-                a = DeviceArray.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
-            return a, a.ptr
-        if isinstance(a, DeviceArray):
-            a = a.to_numpy()
-        a = np.ascontiguousarray(a, dtype=np.uint8)
-        return a, a.ctypes.data
 
     def _add(self, keys, mask, counts):
         keys = np.ascontiguousarray(keys, dtype=self._dtype)
@@ -271,22 +282,6 @@ class _CounterBase:
         self._add(keys, mask, counts)
 
     # ---- reading ---------------------------------------------------------------
-    def _info(self):
-        vals = [ctypes.c_int64() for _ in range(3)]
-        _lib.call("vh_counter_info", self._handle, *[ctypes.byref(v) for v in vals])
-        return [v.value for v in vals]
-
-    def __len__(self):
-        return self._info()[0]
-
-    def length(self):
-        return len(self)
-
-    nan_count = property(lambda self: self._info()[1])
-    null_count = property(lambda self: self._info()[2])
-    has_nan = property(lambda self: self._info()[1] > 0)
-    has_null = property(lambda self: self._info()[2] > 0)
-
     def _read(self, order, dropnan, dropmissing):
         n = len(self)
         keys = np.empty(n, dtype=self._dtype)
@@ -318,21 +313,9 @@ class _CounterBase:
         reverse of that (expression.py:1026-1050); only the answer crosses the host link."""
         return self._read(1 if ascending else 2, dropnan, dropmissing)
 
-    def __sizeof__(self):
-        return len(self) * 16
-
     def __reduce__(self):
         keys, counts, null_index = self._read(0, False, False)
         return (type(self), (keys, counts, null_index))
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h:
-            try:
-                _lib.call("vh_counter_destroy", h)
-            except Exception:
-                pass
-            self._handle = None
 
 
 # keys of <= 4 bytes the index probe's LDS route holds (index.hip IX_LDS_BYTES = 64 KiB = 8192
@@ -341,7 +324,7 @@ class _CounterBase:
 INDEX_LDS_KEYS = 4096
 
 
-class _IndexHashBase:
+class _IndexHashBase(_HashBase):
     """``index_hash_<dtype>`` (``hash_primitives.hpp:623-900``; bindings
     ``hash_primitives.cpp:53-69``): key -> the first row it was seen at, plus the other rows
     of duplicated keys, over the GPU index of libvaexhip -- the hash map of ``DataFrame.join``.
@@ -353,12 +336,10 @@ class _IndexHashBase:
     index holds none gives ``-1`` (the reference leaves that entry uninitialised).  The first
     probe seals the index: ``update`` and ``merge`` raise after it.
     ``index_hash_<t>(initial_capacity=16)`` starts the table at 16 slots."""
-    _dtype = "int64"
+    _prefix = "vh_index"
 
     def __init__(self, *args, initial_capacity=0):
-        h = ctypes.c_void_p()
-        _lib.call("vh_index_create", _lib.DTYPE_CODE[self._dtype], int(initial_capacity), ctypes.byref(h))
-        self._handle = h.value
+        self._create(int(initial_capacity))
 
     # ---- building --------------------------------------------------------------
     def _keys(self, ar):
@@ -376,21 +357,14 @@ class _IndexHashBase:
     def update(self, ar, *args, **kwargs):
         """update(keys[, mask], start_index=0, select=None): row i is row ``start_index + i``;
         rows where select == 0 are not seen at all."""
-        mask = None
-        rest = list(args)
-        if rest and (isinstance(rest[0], (np.ndarray, list, DeviceArray)) or rest[0] is None):
-            mask = rest.pop(0)
-        mask = kwargs.pop("mask", mask)
+        ar, mask, rest = self._update_args(ar, args, kwargs)
         start_index = kwargs.pop("start_index", rest.pop(0) if rest else 0)
         select = kwargs.pop("select", None)
-        if np.ma.isMaskedArray(ar):
-            m = np.ma.getmaskarray(ar)
-            mask = m if mask is None else (np.asarray(mask, bool) | m)
         ar = self._keys(ar)
         device = isinstance(ar, DeviceArray)
         kptr, n, _, _, loc, keep = _column(ar)
-        mkeep, mptr = _CounterBase._side(mask, device)
-        skeep, sptr = _CounterBase._side(select, device)
+        mkeep, mptr = self._side(mask, device)
+        skeep, sptr = self._side(select, device)
         if n:
             _lib.call("vh_index_update", self._handle, kptr, mptr, sptr, n, int(start_index), loc)
 
@@ -401,23 +375,11 @@ class _IndexHashBase:
 
     # ---- reading ---------------------------------------------------------------
     def _info(self):
-        vals = [ctypes.c_int64() for _ in range(5)]
         dup = ctypes.c_int()
-        _lib.call("vh_index_info", self._handle, *[ctypes.byref(v) for v in vals], ctypes.byref(dup))
-        return [v.value for v in vals] + [bool(dup.value)]
+        return super()._info(ctypes.byref(dup)) + [bool(dup.value)]
 
-    def __len__(self):
-        return self._info()[0]
-
-    def length(self):
-        return len(self)
-
-    nan_count = property(lambda self: self._info()[1])
-    null_count = property(lambda self: self._info()[2])
     nan_value = property(lambda self: self._info()[3])
     null_value = property(lambda self: self._info()[4])
-    has_nan = property(lambda self: self._info()[1] > 0)
-    has_null = property(lambda self: self._info()[2] > 0)
     has_duplicates = property(lambda self: self._info()[5])
 
     def _map(self, values, mask, out):
@@ -437,7 +399,7 @@ class _IndexHashBase:
             if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable):
                 raise TypeError("map_index: out must be a contiguous writeable array")
             optr, oloc = out.ctypes.data, _lib.LOC_HOST
-        mkeep, mptr = _CounterBase._side(mask, device)
+        mkeep, mptr = self._side(mask, device)
         if mkeep is not None and len(mkeep) != n:
             raise ValueError("map_index: mask and values differ in length")
         found = ctypes.c_int(0)
@@ -470,7 +432,7 @@ class _IndexHashBase:
         start_index = int(rest.pop(0)) if rest else 0
         values = self._keys(values)
         device = isinstance(values, DeviceArray)
-        mkeep, mptr = _CounterBase._side(mask, device)
+        mkeep, mptr = self._side(mask, device)
         n_out = ctypes.c_uint64(0)
         kptr = values.ptr if device else values.ctypes.data
         # the pairs are counted and kept in the library, then read with a second call
@@ -485,19 +447,6 @@ class _IndexHashBase:
         _lib.call("vh_index_map_index_duplicates", self._handle, None, None, 0, 0, _lib.LOC_HOST, ctypes.byref(n_out),
                   lptr, rptr)
         return left, right
-
-    def __sizeof__(self):
-        return len(self) * 16
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h:
-            try:
-                _lib.call("vh_index_destroy", h)
-            except Exception:
-                pass
-            self._handle = None
-
 
 def take_device(columns, indices, with_mask=False):
     """Device gather (vh_take): ``[c[indices] for c in columns]`` for DeviceArray columns and a
