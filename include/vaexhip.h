@@ -117,7 +117,9 @@ int vh_timing_read(const char *kernel, uint64_t *launches, double *total_ms);
 int vh_stream(void **stream);
 /* engine statistics since the last reset (this device): "tile_overflow_rows" (tile path rows
  * that missed their pass-A region and took global atomics), "hashagg_overflow_rows",
- * "set_overflow_rows" (the groupby / ordered_set partition overflow paths) */
+ * "set_overflow_rows" (the groupby / ordered_set partition overflow paths); the maximum since
+ * the last reset, every device: "tile_stream_rounds" (rounds of the longest segment walk of a
+ * tile path pass-B unit in the stream layout, counted on the host from the planned units) */
 int vh_stat_read(const char *name, uint64_t *value, int reset);
 
 /* ---- Binners: superagg_binners.cpp ------------------------------------- */

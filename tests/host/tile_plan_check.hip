@@ -7,7 +7,10 @@
 //                             kernel / plan invariant on its own
 //   tile_plan_check resolve   every pass-A / pass-B descriptor the matrix produced resolves to a
 //                             kernel of libvaexhip.so (addresses only; nothing is launched)
+//   tile_plan_check rounds NAME=ROWS ...   the most rounds a pass-B unit of plan NAME walks over ROWS
+//                             rows at occupancy 1..4 (rounds_mode below)
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -327,7 +330,105 @@ static bool stage3_pick(const std::string &n) {
            n == "f32x2/count+sumf32/c2" || n == "ord32/count+sum/c1" || n == "f64x2/count+sum/c0";
 }
 
+// ---- rounds mode: the plans of tests/test_gpu_stream_rounds.py (tests/stream_rounds_cases.py names
+// them and gives each its row count).  A sample of cold tiles -- every tile but three hot ones holds
+// about half of the n / (4 cus) rows at which plan_units starts to split a tile -- goes through stages 1-3 at
+// occupancy 1..4, and the most rounds a unit walks (max_unit_rounds) is printed per occupancy, with
+// whether pass A's workgroups differ in their commit counts (the tile table's empty tail rows).
+static void make_cold_sample(uint32_t T, uint64_t sblocks, int cus, std::vector<uint64_t> &hist, std::vector<uint32_t> &brange) {
+    hist.assign(2 * (size_t)T, 0);
+    brange.assign(2 * (size_t)sblocks + 2, 0);
+    const uint64_t B = TA_BATCH, cold = B * 7 / (10 * 4 * (uint64_t)cus);
+    const uint32_t h0 = T / 2 - 1;
+    for (uint64_t b = 0; b < sblocks; b++) {
+        brange[2 * b] = 0, brange[2 * b + 1] = T - 1;
+        for (uint32_t t = 0; t < T; t++) {
+            const uint64_t c = t >= h0 && t < h0 + 3 ? (B - cold * (T - 3)) / 3 : cold;
+            hist[t] += c, hist[T + t] += c * c;
+        }
+    }
+}
+
+static bool rounds_plan(const std::string &name, Case &c) {
+    const int V = 20, V2 = 21;
+    // 1024^2, 700^2 and 64^3 bins with their edge cells; ~1e6 keys with the sampled range's margin.  700^2: plans
+    // of 20 or more LDS bytes per cell have 4096-cell tiles, and past 136 tiles the staging of three batches
+    // leaves no room for the wide stream-out, which the stream layout needs
+    const uint64_t c2 = 1027 * 1027, c7 = 703 * 703, c3 = 67 * 67 * 67, cg = 1062600;
+    std::vector<BinnerDev> f64x2 = {scalar_binner(VH_F64, 0), scalar_binner(VH_F64, 1)};
+    std::vector<BinnerDev> f64x3 = {scalar_binner(VH_F64, 0), scalar_binner(VH_F64, 1), scalar_binner(VH_F64, 2)};
+    std::vector<BinnerDev> f32x2 = {scalar_binner(VH_F32, 0), scalar_binner(VH_F32, 1)};
+    BinnerDev key = scalar_binner(VH_I32, 0, 8);
+    key.kind = 1, key.ordinal_count = 1062597;
+    const FusedAgg cnt = agg(VH_AGG_COUNT), sum = agg(VH_AGG_SUM, VH_F64, V), sum2 = agg(VH_AGG_SUM, VH_F64, V2);
+    const FusedAgg cntv = agg(VH_AGG_COUNT, VH_F64, V), mn = agg(VH_AGG_MIN, VH_F64, V), mx = agg(VH_AGG_MAX, VH_F64, V);
+    if (name == "c2") c = make_case(name, f64x2, {cnt, sum}, 0, c2);
+    else if (name == "mm_simple") c = make_case(name, f64x2, {cnt, sum, mn, mx}, 0, c7);
+    else if (name == "minmax") c = make_case(name, f64x2, {mn, mx}, 0, c2);
+    else if (name == "2sum2d") c = make_case(name, f64x2, {cnt, sum, sum2}, 0, c2);
+    else if (name == "2sum3d") c = make_case(name, f64x3, {cnt, sum, sum2}, 0, c3);
+    else if (name == "var") c = make_case(name, f64x2, {agg(VH_AGG_SUM_MOMENT, VH_F64, V, 16, 2), sum, cntv}, 0, c7);
+    else if (name == "moment3") c = make_case(name, f64x2, {cntv, sum, agg(VH_AGG_SUM_MOMENT, VH_F64, V, 16, 3)}, 0, c7);
+    else if (name == "f32") c = make_case(name, f32x2, {cnt, agg(VH_AGG_SUM, VH_F32, V)}, 0, c2);
+    else if (name == "ord_f64") c = make_case(name, {key}, {sum, cnt}, 0, cg);
+    else if (name == "ord_i8f32")  // with the groupby's own count(*): 20 bytes per cell, so half the key range
+        c = make_case(name, {key}, {agg(VH_AGG_SUM, VH_I8, V), agg(VH_AGG_SUM, VH_F32, V2), cnt}, 0, cg / 2);
+    else if (name == "ord_f64_mask") c = make_case(name, {key}, {sum, cnt}, 0, cg), c.rowmask = true;
+    else return false;
+    return true;
+}
+
+static int rounds_mode(int argc, char **argv) {
+    const int cus = 256;
+    int bad = 0;
+    printf("TB_SEGS=%u ceiling=%llu\n", TB_SEGS, (unsigned long long)(TB_ROUNDS * TB_THREADS / TB_SEGS));
+    for (int i = 2; i < argc; i++) {
+        const std::string arg = argv[i];
+        const size_t eq = arg.find('=');
+        Case c;
+        if (eq == std::string::npos || !rounds_plan(arg.substr(0, eq), c)) {
+            printf("%s unknown\n", arg.c_str());
+            bad++;
+            continue;
+        }
+        c.n = strtoull(arg.c_str() + eq + 1, nullptr, 10);
+        // try_tiled (tiled.hip): the pair-load kernels tile all rows but the last of an odd n
+        if ((c.n & 1) && !c.fa.generic_vals && (c.nd_f64 > 0 || ord_fast_ok(c.plan, c.fa))) c.n--;
+        Ctx x;
+        Rec1 r1;
+        if (!stage1(c, x, r1)) {
+            printf("%s -\n", c.name.c_str());
+            bad++;
+            continue;
+        }
+        printf("%s n=%llu T=%d sb=%d", c.name.c_str(), (unsigned long long)c.n, r1.T, r1.sb);
+        for (int occ = 1; occ <= 4; occ++) {
+            Rec2 r2;
+            stage2(c, x, cus, occ, r2);
+            std::vector<uint64_t> hist;
+            std::vector<uint32_t> brange;
+            make_cold_sample((uint32_t)r1.T, r2.sblocks, cus, hist, brange);
+            TileRegions reg;
+            std::vector<WorkUnit> units;
+            uint32_t rounds = 0;
+            if (size_regions(x.tp, x.L, c.n, hist.data(), brange.data(), reg)) {
+                plan_units(x.tp, x.L, c.n, cus, hist.data(), reg.sampled, units);
+                rounds = max_unit_rounds(x.L, units);
+            }
+            // workgroup w takes batches w, w + W, ...: the commit counts of the first and the last differ
+            const uint64_t nb = (c.n + TA_BATCH - 1) / TA_BATCH, W = r2.W, sb = (uint64_t)r1.sb;
+            const uint64_t last = nb >= W ? (nb - (W - 1) + W - 1) / W : 0;
+            const int tail = (r2.kbat + sb - 1) / sb != (last + sb - 1) / sb;
+            printf(" | occ%d W=%llu ncw=%llu st=%llu g=%llu rounds=%u tail=%d", occ, (unsigned long long)r2.W, (unsigned long long)r2.ncw,
+                   (unsigned long long)r2.stream_layout, (unsigned long long)r2.g_min, rounds, tail);
+        }
+        printf("\n");
+    }
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::string(argv[1]) == "rounds") return rounds_mode(argc, argv);
     const bool resolve = argc > 1 && std::string(argv[1]) == "resolve";
     std::vector<Case> cases;
     build_matrix(cases);

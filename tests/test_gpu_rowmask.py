@@ -193,3 +193,100 @@ def test_selection_mask_cache_follows_select():
     got = np.asarray(df.count(binby="x", limits=[-4, 4], shape=64, selection=True))
     want = oracle.extract_central_part(oracle.compute_grid([spec], "count", mask=(w2 > 0.7).astype(np.uint8)))
     np.testing.assert_array_equal(got, want)
+
+
+def _replace_repeatedly(make, install, query, times=6):
+    """Replaces one HBM column `times` times with fresh arrays of equal length, keeping no old
+    array referenced; after each replacement `query(host array)` checks a masked result.
+    Returns the device addresses the column had, in order."""
+    from vaex_amd.device import DeviceArray
+    ptrs = []
+    for _ in range(times + 1):
+        host = make()
+        col = DeviceArray.from_numpy(host)  # allocated while the column it replaces is alive ...
+        ptrs.append(col.ptr)
+        install(col)                        # ... which is freed here: its block goes back to the
+        del col                             # runtime's cache, and the next allocation takes it
+        query(host)
+    return ptrs
+
+
+def test_filter_mask_cache_survives_address_reuse():
+    """A filtered HBM frame whose column is replaced again and again with arrays of equal
+    length: the block cache (runtime.hip, dev_alloc: exact sizes, the longest-freed block
+    first) hands a replaced array's address to a later one, and a mask cache that remembered
+    addresses would return the earlier array's mask for it.  Every groupby sum is that of
+    the current array's own mask, and an address did recur."""
+    import vaex_amd
+    from vaex_amd.device import DeviceArray
+    rng = np.random.default_rng(31)
+    n = 1_000_000
+    keys = rng.integers(0, 10_000, n).astype(np.int32)
+    base = vaex_amd.from_arrays(key=DeviceArray.from_numpy(keys), v=DeviceArray.from_numpy(np.zeros(n)))
+    dff = base[base.v > 0]
+
+    def query(v):
+        for _ in range(2):  # the second query reuses the mask
+            g = dff.groupby("key", agg={"v": "sum"})
+            want = oracle.groupby_agg({"key": keys[v > 0], "v": v[v > 0]}, ["key"], [("v", "sum", "v")])
+            np.testing.assert_array_equal(g["key"].to_numpy(), want["key"])
+            np.testing.assert_allclose(g["v"].to_numpy(), want["v"], rtol=1e-9, atol=1e-12)
+
+    ptrs = _replace_repeatedly(lambda: rng.normal(size=n), lambda col: dff.columns.__setitem__("v", col), query)
+    print("addresses of v:", [hex(p) for p in ptrs])
+    assert len(set(ptrs)) < len(ptrs), "no address recurred: the test did not meet the case it is there for"
+
+
+def test_selection_mask_cache_survives_address_reuse():
+    """The same for a selection mask kept through device_keep_mask(cache=True): df.select and
+    count(selection=True) after each replacement of the selected column."""
+    import vaex_amd
+    from vaex_amd.device import DeviceArray
+    rng = np.random.default_rng(32)
+    n = 1_000_000
+    x = rng.normal(size=n)
+    df = vaex_amd.from_arrays(x=DeviceArray.from_numpy(x), w=DeviceArray.from_numpy(np.zeros(n)))
+    df.select("w > 0.5")
+    spec = oracle.Binner("scalar", x, vmin=-4, vmax=4, bins=64)
+
+    def query(w):
+        for _ in range(2):
+            got = np.asarray(df.count(binby="x", limits=[-4, 4], shape=64, selection=True))
+            want = oracle.extract_central_part(oracle.compute_grid([spec], "count", mask=(w > 0.5).astype(np.uint8)))
+            np.testing.assert_array_equal(got, want)
+
+    ptrs = _replace_repeatedly(lambda: rng.random(n), lambda col: df.columns.__setitem__("w", col), query)
+    print("addresses of w:", [hex(p) for p in ptrs])
+    assert len(set(ptrs)) < len(ptrs), "no address recurred: the test did not meet the case it is there for"
+
+
+def test_filter_mask_cache_reads_variables_by_value():
+    """A filter that names a variable, set in a loop to float objects built at run time: CPython
+    hands a freed float's id() to a later one, and a mask cache that remembered ids would
+    return the earlier threshold's mask.  Every count is that of the current threshold, an
+    id() did recur, and an equal value in a new object reuses the mask."""
+    import vaex_amd
+    from vaex_amd.device import DeviceArray
+    rng = np.random.default_rng(33)
+    n = 1_000_000
+    x, w = rng.normal(size=n), rng.random(n)
+    base = vaex_amd.from_arrays(x=DeviceArray.from_numpy(x), w=DeviceArray.from_numpy(w))
+    base.add_variable("thr", 0.0)
+    dff = base.filter("w > thr")
+    spec = oracle.Binner("scalar", x, vmin=-4, vmax=4, bins=64)
+    ids = []
+    for k in range(8):
+        thr = float(f"0.{k % 4 + 1}5")  # a new float object each time, never referenced elsewhere
+        ids.append(id(thr))
+        dff.variables["thr"] = thr
+        del thr
+        t = dff.variables["thr"]
+        got = np.asarray(dff.count(binby="x", limits=[-4, 4], shape=64))
+        want = oracle.extract_central_part(oracle.compute_grid([spec], "count", mask=(w > t).astype(np.uint8)))
+        np.testing.assert_array_equal(got, want)
+    print("ids of thr:", ids)
+    assert len(set(ids)) < len(ids), "no id() recurred: the test did not meet the case it is there for"
+    masks = len(dff._filter_mask_cache)
+    dff.variables["thr"] = float("0.45")  # the last threshold again, in a new object
+    np.testing.assert_array_equal(np.asarray(dff.count(binby="x", limits=[-4, 4], shape=64)), got)
+    assert len(dff._filter_mask_cache) == masks

@@ -117,6 +117,45 @@ def test_host_expression_evaluation():
     assert df.data_type("x") == np.float64
 
 
+def test_device_mask_cache_keys_on_live_objects_and_values(monkeypatch):
+    """DataFrame._cached_device_mask without a GPU (the evaluation is a stub that counts):
+    a hit needs the frame's current column objects and equal variable values, whatever
+    addresses or id()s they have; a replaced column's entry is dropped, not kept alive."""
+    import gc
+    import weakref
+
+    import vaex_amd
+    from vaex_amd.dataframe import DataFrame
+    calls = []
+    monkeypatch.setattr(DataFrame, "_eval_device", lambda self, expr, i1, i2: calls.append(expr) or object())
+    df = vaex_amd.from_arrays(x=np.arange(8.0), w=np.arange(8.0))
+    df.add_variable("thr", 0.25)
+    m = df._cached_device_mask("w > thr", 0, 8)
+    assert df._cached_device_mask("w > thr", 0, 8) is m and len(calls) == 1
+    assert df.copy()._cached_device_mask("w > thr", 0, 8) is m  # copies share the cache
+    assert df._cached_device_mask("w > thr", 0, 4) is not m and len(calls) == 2
+    df.variables["thr"] = float("0.25")  # an equal value in another object
+    assert df._cached_device_mask("w > thr", 0, 8) is m
+    for other in (0.5, np.float32(0.25), -0.0, 0.0, 0):  # another value, another type of an equal value, the zeros
+        df.variables["thr"] = other
+        before = len(calls)
+        assert df._cached_device_mask("w > thr", 0, 8) is not m and len(calls) == before + 1
+    df.variables["thr"] = 0.25
+    del df._filter_mask_cache[:]
+    m = df._cached_device_mask("w > thr", 0, 8)
+    old = weakref.ref(df.columns["w"])
+    df.columns["w"] = np.arange(8.0)  # an equal column in another object
+    gc.collect()
+    assert old() is None, "the cache keeps a replaced column alive"
+    before = len(calls)
+    m2 = df._cached_device_mask("w > thr", 0, 8)
+    assert m2 is not m and len(calls) == before + 1
+    assert all(e[3] is not m for e in df._filter_mask_cache), "the replaced column's mask is still held"
+    for k in range(20):  # bounded
+        df._cached_device_mask(f"w > {k}", 0, 8)
+    assert len(df._filter_mask_cache) <= 8
+
+
 def test_hostops_match_numpy():
     """Threaded host finishing (mean division, label ranges) equals the single numpy call."""
     from vaex_amd import hostops

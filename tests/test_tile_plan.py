@@ -31,6 +31,34 @@ def test_planner_decisions_match_the_recorded_ones():
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
 
 
+def test_stream_round_shapes_walk_several_rounds():
+    """The (plan, rows) pairs of tests/test_gpu_stream_rounds.py (tests/stream_rounds_cases.py)
+    through stages 1-3 with a sample of cold tiles, 256 CUs, pass-A occupancy 1..4: each takes
+    the stream layout and has a work unit of at least two rounds of TB_SEGS segments, the pairs
+    meant for the ceiling exactly TB_ROUNDS * TB_THREADS / TB_SEGS, and the tail pairs leave
+    pass-A workgroups with different commit counts -- so a change of VH_TA_SB, TA_BATCH or
+    TB_ROUNDS cannot make the GPU tests vacuous unnoticed."""
+    from stream_rounds_cases import CASES, TAIL_CASES
+    res = _run("rounds", *[f"{plan}={n}" for plan, n, _ in CASES.values()])
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    head, *lines = res.stdout.splitlines()
+    ceiling = int(head.split("ceiling=")[1])
+    assert len(lines) == len(CASES)
+    for (name, (plan, n, want)), line in zip(CASES.items(), lines):
+        first, *occs = line.split(" | ")
+        assert first.split()[0] == plan and f"n={n - n % 2}" in first.split(), line
+        assert len(occs) == 4
+        for occ in occs:
+            f = dict(kv.split("=") for kv in occ.split()[1:])
+            assert f["st"] == "1", f"{name}: no stream layout: {line}"
+            if want is None:
+                assert int(f["rounds"]) >= 2, f"{name}: {line}"
+            else:
+                assert int(f["rounds"]) == want == ceiling, f"{name}: {line}"
+            if name in TAIL_CASES:
+                assert f["tail"] == "1", f"{name}: equal commit counts: {line}"
+
+
 def test_every_kernel_descriptor_resolves():
     res = _run("resolve")
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]

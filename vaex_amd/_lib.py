@@ -220,7 +220,8 @@ def synchronize():
 
 
 def stat_read(name, reset=True):
-    """An engine statistic (vh_stat_read), e.g. "tile_overflow_rows"."""
+    """An engine statistic (vh_stat_read), e.g. "tile_overflow_rows", or "tile_stream_rounds":
+    the most rounds a pass-B unit of a stream-layout tile launch walked since the last reset."""
     v = ctypes.c_uint64()
     call("vh_stat_read", name.encode(), ctypes.byref(v), int(bool(reset)))
     return v.value

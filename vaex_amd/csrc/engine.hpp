@@ -200,6 +200,8 @@ bool try_tiled(const BinPlan &plan, const FusedAggs &fa, uint64_t n, uint64_t ce
 uint64_t stat_tile_overflow(bool reset);
 uint64_t stat_hashagg_overflow(bool reset);
 uint64_t stat_set_overflow(bool reset);
+// the most rounds a pass-B unit of a stream-layout launch walked (tile_plan.hpp: unit_rounds)
+uint64_t stat_tile_stream_rounds(bool reset);
 // AggFirst over a grid too large for LDS through the tile-partitioned exchange (first.hip):
 // fills the aggregator's s_key / s_row scratch for rows [0, n) of this chunk (global rows
 // row0 + j); false when not eligible or when its resolve list overflowed (scratch reset)

@@ -807,6 +807,7 @@ int vh_stat_read(const char *name, uint64_t *value, int reset) {
     VH_API_BEGIN
     const std::string n = name ? name : "";
     if (n == "tile_overflow_rows") *value = stat_tile_overflow(reset != 0);
+    else if (n == "tile_stream_rounds") *value = stat_tile_stream_rounds(reset != 0);
     else if (n == "hashagg_overflow_rows") *value = stat_hashagg_overflow(reset != 0);
     else if (n == "set_overflow_rows") *value = stat_set_overflow(reset != 0);
     else if (n == "first_tiled_chunks") *value = stat_first_tiled(reset != 0);

@@ -34,12 +34,14 @@ constexpr uint32_t TILE_MAX_TILES = 4096;
 constexpr size_t LDS_MAX_BYTES = 160 * 1024;  // per workgroup on gfx950
 constexpr int TA_WG_PER_CU = 4;
 constexpr int SAMPLE_BLOCKS = 512;
-// stream layout: a pass-B unit walks (workgroup, commit) segments in rounds of TB_THREADS, at most
-// TB_ROUNDS per unit (a cold tile's single unit would walk all W x ncw segments in one workgroup)
+// stream layout: a pass-B unit walks its (workgroup, commit) segments in rounds of TB_SEGS (two per
+// thread), at most TB_ROUNDS * TB_THREADS segments per unit (a cold tile's single unit would walk
+// all W x ncw segments in one workgroup): TB_ROUNDS * TB_THREADS / TB_SEGS rounds at the most
 #ifndef VH_TB_ROUNDS
 #define VH_TB_ROUNDS 6
 #endif
 constexpr uint64_t TB_ROUNDS = VH_TB_ROUNDS;
+constexpr uint32_t TB_SEGS = 2 * TB_THREADS;
 
 enum : int32_t { CNT_ALWAYS = -2, CNT_FLAG = -1 };
 
@@ -649,6 +651,21 @@ inline void plan_units(const TilePlan &pl, const TileLaunch &L, uint64_t n, int 
         units.swap(sorted);
     }
     if (units.size() > L.max_units) fail(VH_ERR_RUNTIME, "tiled binning: work-unit table overflow");
+}
+
+// Rounds of pass B's segment walk over one work unit (k_tile_reduce: its `rounds`).  Stream layout:
+// the unit's (w_end - w_begin) * ncw segments in rounds of TB_SEGS; regions: one round.
+inline uint32_t unit_rounds(const TileLaunch &L, const WorkUnit &u) {
+    if (!L.stream_layout) return 1;
+    return (uint32_t)(((uint64_t)(u.w_end - u.w_begin) * L.ncw + TB_SEGS - 1) / TB_SEGS);
+}
+// the most rounds any unit of a launch walks (vh_stat_read("tile_stream_rounds") records it for
+// stream-layout launches).  A cold tile (g = g_min units) walks the most: about
+// ceil(n / TA_BATCH) / sb segments, so more than one round takes n > TB_SEGS * TA_BATCH * sb rows
+inline uint32_t max_unit_rounds(const TileLaunch &L, const std::vector<WorkUnit> &units) {
+    uint32_t r = 0;
+    for (const WorkUnit &u : units) r = std::max(r, unit_rounds(L, u));
+    return r;
 }
 
 }  // namespace vh

@@ -1519,6 +1519,7 @@ __global__ __launch_bounds__(TBT) void k_tile_reduce(FusedAggs fa, TileParams tp
     // first entry -- regions: absolute (u64 s_rbase); segments: the offset in their pass-A
     // workgroup's stream (u32 s_a; the workgroup follows from the segment index)
     constexpr uint32_t SEGS = 2 * TBT;
+    static_assert(TBT != TB_THREADS || SEGS == TB_SEGS, "the host counts a unit's rounds in TB_SEGS (unit_rounds)");
     __shared__ uint32_t s_fill[SEGS + 1];
     __shared__ uint32_t s_pre[SEGS + 2];
     __shared__ uint64_t s_b64[1024 + 1];  // s_rbase and s_a share it (one mode per launch)
@@ -2161,6 +2162,10 @@ static void launch(const void *kernel, unsigned grid, unsigned block, size_t lds
     VH_HIP(hipGetLastError());
 }
 
+// the most rounds a pass-B unit of a stream-layout launch walked since the last reset (host
+// arithmetic of the planned units, every device; vh_stat_read("tile_stream_rounds"))
+static std::atomic<uint64_t> g_tile_stream_rounds{0};
+
 static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64,
                            const uint8_t *rowmask, const TileSwitches &sw) {
     TileScratch &ws = tile_scratch();
@@ -2253,6 +2258,11 @@ static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t
     if (!size_regions(tpl, L, n, hist, brange, reg)) return false;
     std::vector<WorkUnit> units;
     plan_units(tpl, L, n, cu_count(), hist, reg.sampled, units);
+    if (L.stream_layout) {  // vh_stat_read("tile_stream_rounds"): the most rounds a unit walks
+        const uint64_t r = max_unit_rounds(L, units);
+        uint64_t seen = g_tile_stream_rounds.load(std::memory_order_relaxed);
+        while (seen < r && !g_tile_stream_rounds.compare_exchange_weak(seen, r, std::memory_order_relaxed)) {}
+    }
     if (!L.stream_layout) setup(reg.stride, reg.stotal);
     char *upl = tstage.as<char>() + dl_bytes;  // upload region: cap | toff | sstart | scap | units
     auto upload = [&](uint64_t meta_off, const void *src, uint64_t bytes) {
@@ -2349,6 +2359,10 @@ uint64_t stat_tile_overflow(bool reset) {
         VH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(d_tile_overflow_rows), &z, sizeof(z)));
     }
     return v;
+}
+
+uint64_t stat_tile_stream_rounds(bool reset) {
+    return reset ? g_tile_stream_rounds.exchange(0) : g_tile_stream_rounds.load();
 }
 
 }  // namespace vh

@@ -16,6 +16,8 @@ here are column names, or numpy expressions over host columns evaluated per chun
 """
 import ast
 import re
+import threading
+import weakref
 
 import numpy as np
 
@@ -31,6 +33,31 @@ default_shape = 128
 
 class RowLimitException(ValueError):
     pass
+
+
+_mask_cache_lock = threading.Lock()
+
+
+def _column_ref(col):
+    """A callable giving the column while it is alive: a weak reference where the type has one."""
+    try:
+        return weakref.ref(col)
+    except TypeError:
+        return lambda: col
+
+
+def _variable_value(v):
+    """What the mask cache remembers of a variable: a scalar's type and value (its repr also
+    tells -0.0 from 0.0 and matches NaN with NaN); any other object itself, compared by identity
+    and held so that its id() cannot be handed out again."""
+    if v is None or isinstance(v, (bool, int, float, complex, str, bytes, np.generic)):
+        return (type(v), repr(v))
+    return (None, v)
+
+
+def _same_variables(a, b):
+    return len(a) == len(b) and all(x[0] is y[0] and (x[1] == y[1] if x[0] is not None else x[1] is y[1])
+                                    for x, y in zip(a, b))
 
 
 def _ensure_string(e):
@@ -225,9 +252,9 @@ class DataFrame:
         df._categories = dict(self._categories)
         df.selection_expressions = dict(self.selection_expressions)
         df._filter = self._filter
-        # copies share the filter-mask cache (its keys hold the filter and the columns, so a
-        # copy that changes either misses; groupby works on a copy)
-        df._filter_mask_cache = self.__dict__.setdefault("_filter_mask_cache", {})
+        # copies share the filter-mask cache (its entries name the filter and the column objects,
+        # so a copy that changes either misses; groupby works on a copy)
+        df._filter_mask_cache = self.__dict__.setdefault("_filter_mask_cache", [])
         return df
 
     def add_column(self, name, data):
@@ -371,15 +398,25 @@ class DataFrame:
         return np.asarray(self._eval_host(self._filter, i1, i2), dtype=bool)
 
     def _cached_device_mask(self, expr, i1, i2):
-        key = (expr, i1, i2,
-               tuple((k, getattr(c, "ptr", id(c)), len(c)) for k, c in self.columns.items()),
-               tuple(sorted(self.virtual_columns.items())), tuple((k, id(v)) for k, v in self.variables.items()))
-        cache = self.__dict__.setdefault("_filter_mask_cache", {})
-        m = cache.get(key)
-        if m is None:
+        # An entry is (key, column references, variable values, mask).  A hit needs the frame's
+        # current column objects to be the live ones the mask was computed from and its variables
+        # to hold the same values: a device pointer or an id() names whatever was allocated there
+        # last (the block cache and CPython's free lists hand both out again), so neither is
+        # remembered.  Columns are held weakly: a replaced column's HBM is not kept alive here,
+        # and an entry with a dead column goes, its mask with it.
+        key = (expr, i1, i2, tuple(self.columns), tuple(sorted(self.virtual_columns.items())), tuple(self.variables))
+        cols, values = list(self.columns.values()), [_variable_value(v) for v in self.variables.values()]
+        cache = self.__dict__.setdefault("_filter_mask_cache", [])
+        with _mask_cache_lock:
+            cache[:] = [e for e in cache if all(r() is not None for r in e[1])]
+            for k, refs, vals, m in cache:
+                if k == key and all(r() is c for r, c in zip(refs, cols)) and _same_variables(vals, values):
+                    return m
+        m = self._eval_device(expr, i1, i2)
+        with _mask_cache_lock:
             if len(cache) >= 8:
-                cache.clear()
-            m = cache[key] = self._eval_device(expr, i1, i2)
+                del cache[:]
+            cache.append((key, [_column_ref(c) for c in cols], values, m))
         return m
 
     def data_type(self, expression):
