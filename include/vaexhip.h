@@ -406,6 +406,30 @@ int vh_hashagg_exchange(vh_hashagg *h, vh_comm *comm, int gather);
 int vh_expr_eval(const uint32_t *code, int ncode, const uint64_t *consts, int nconsts, const void *const *cols,
                  const int *col_dtypes, int ncols, uint64_t n, int out_dtype, void *out);
 
+/* ---- selections on HBM columns (select.hip) ---------------------------------
+ * how a selection combines with the one before it (selections.py:11-36 _select_functions);
+ * with no previous mask and / or / xor give the new mask and subtract its complement */
+enum vh_select_mode {
+    VH_SELECT_REPLACE = 0, VH_SELECT_AND = 1, VH_SELECT_OR = 2, VH_SELECT_XOR = 3, VH_SELECT_SUBTRACT = 4
+};
+/* The lasso (SelectionLasso.evaluate, selections.py:172-204, over vaexfast.cpp:1757-1775
+ * pnpoly): mask[i] = mode(prev[i] == 1, inside(x[i], y[i])) as 0 / 1 bytes; prev may be NULL.
+ * x / y: HBM columns of float64 or float32 (each its own dtype), read as float64; prev / out:
+ * HBM, out may be prev.  vertx / verty: host arrays of nvert >= 0 vertices (nvert = 0: nothing
+ * is inside); only they are copied to the device, and nothing is read back.  inside() is the
+ * reference's arithmetic in float64, operation for operation (IEEE division, no contraction):
+ *   d = (tx-meanx)*(tx-meanx) + (ty-meany)*(ty-meany);  inside = 0 unless d < radius*radius
+ *   for i, j = i-1 (j = nvert-1 for i = 0):
+ *     if ((vy[i] > ty) != (vy[j] > ty)) && (tx < (vx[j]-vx[i]) * (ty-vy[i]) / (vy[j]-vy[i]) + vx[i])  c = !c
+ * so the mask equals the C loop's bit for bit (NaN / inf coordinates are never inside).
+ * VH_ERR_ARG: another dtype, nvert < 0, an unknown mode, a null column with n > 0. */
+int vh_pnpoly(const void *x, int x_dtype, const void *y, int y_dtype, uint64_t n, const double *vertx,
+              const double *verty, int nvert, double meanx, double meany, double radius, const uint8_t *prev, int mode,
+              uint8_t *out);
+/* out = mode(a == 1, b == 1) as 0 / 1 bytes; b NULL: out = !(a == 1).  HBM buffers; out may be
+ * a or b.  Only bytes equal to 1 count as selected, as everywhere in the engine. */
+int vh_mask_combine(const uint8_t *a, const uint8_t *b, int mode, uint64_t n, uint8_t *out);
+
 /* combined int64 key of a multi-key groupby, out[i] = sum_j (cols[j][i] - mins[j]) * mults[j]
  * (the cartesian ordinal of groupby.py:248-288 _combine, first key most significant);
  * HBM columns and output, up to 8 integer key columns */

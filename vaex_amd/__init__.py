@@ -12,6 +12,7 @@ reference's plugin surface for that path:
 * :mod:`vaex_amd.distributed` -- row sharding over GPUs + RCCL grid reduce
 * :mod:`vaex_amd.hdf5`       -- memory-mapped vaex HDF5 files (read + export), no h5py
 * :mod:`vaex_amd.expr`       -- expressions / selections / filters evaluated on the GPU
+* :mod:`vaex_amd.selections` -- ``vaex.selections`` (modes, history nodes, the lasso)
 """
 from . import _lib  # noqa: F401  (fails loudly if the HIP library is missing)
 from . import agg, superagg, superutils  # noqa: F401

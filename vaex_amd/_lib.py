@@ -20,6 +20,7 @@ DTYPE_CODE = {name: i for i, name in enumerate(DTYPES)}
 AGG_KIND = {"AggCount": 0, "AggSum": 1, "AggMin": 2, "AggMax": 3, "AggFirst": 4, "AggSumMoment": 5, "AggNUnique": 6,
             "AggCov": 7}
 LOC_AUTO, LOC_HOST, LOC_DEVICE = 0, 1, 2
+SELECT_MODE = {"replace": 0, "and": 1, "or": 2, "xor": 3, "subtract": 4}  # enum vh_select_mode
 
 # every symbol the header declares, with (restype, argtypes)
 _vp, _u64, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int64, ctypes.c_double
@@ -129,6 +130,8 @@ SIGNATURES = {
     "vh_comm_agg_allreduce": (_i32, [_vp, _vp]),
     "vh_hashagg_exchange": (_i32, [_vp, _vp, _i32]),
     "vh_argsort": (_i32, [_u64, _vp, _i32, _vp]),
+    "vh_pnpoly": (_i32, [_vp, _i32, _vp, _i32, _u64, _p(_dbl), _p(_dbl), _i32, _dbl, _dbl, _dbl, _vp, _i32, _vp]),
+    "vh_mask_combine": (_i32, [_vp, _vp, _i32, _u64, _vp]),
     "vh_expr_eval": (_i32, [_p(ctypes.c_uint32), _i32, _p(_u64), _i32, _p(_vp), _p(_i32), _i32, _u64, _i32, _vp]),
 }
 

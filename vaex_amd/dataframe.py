@@ -22,6 +22,7 @@ import weakref
 import numpy as np
 
 from . import agg as vagg
+from . import selections
 from .device import DeviceArray
 from .execution import default_executor
 from .promise import Promise, delayed
@@ -218,7 +219,8 @@ class DataFrame:
         self.variables = {}
         self.virtual_columns = {}
         self._categories = {}
-        self.selection_expressions = {}
+        self.selection_histories = {}         # name -> the selections made under it, oldest first
+        self.selection_history_indices = {}   # name -> index of the current one, -1: none
         self._filter = None
         self.executor = executor or default_executor
         lengths = {len(v) for v in self.columns.values()}
@@ -250,7 +252,7 @@ class DataFrame:
         df.variables = dict(self.variables)
         df.virtual_columns = dict(self.virtual_columns)
         df._categories = dict(self._categories)
-        df.selection_expressions = dict(self.selection_expressions)
+        df._copy_selections(self)
         df._filter = self._filter
         # copies share the filter-mask cache (its entries name the filter and the column objects,
         # so a copy that changes either misses; groupby works on a copy)
@@ -397,7 +399,7 @@ class DataFrame:
             return self._cached_device_mask(self._filter, i1, i2)
         return np.asarray(self._eval_host(self._filter, i1, i2), dtype=bool)
 
-    def _cached_device_mask(self, expr, i1, i2):
+    def _cached_device_mask(self, expr, i1, i2, compute=None):
         # An entry is (key, column references, variable values, mask).  A hit needs the frame's
         # current column objects to be the live ones the mask was computed from and its variables
         # to hold the same values: a device pointer or an id() names whatever was allocated there
@@ -412,7 +414,9 @@ class DataFrame:
             for k, refs, vals, m in cache:
                 if k == key and all(r() is c for r, c in zip(refs, cols)) and _same_variables(vals, values):
                     return m
-        m = self._eval_device(expr, i1, i2)
+        # expr: the expression string, or (with compute) the hashable form of a selection that
+        # is evaluated node by node
+        m = self._eval_device(expr, i1, i2) if compute is None else compute()
         with _mask_cache_lock:
             if len(cache) >= 8:
                 del cache[:]
@@ -432,49 +436,209 @@ class DataFrame:
         v = self._eval_host(expression, 0, min(self._length, 16))
         return np.dtype(v.dtype)
 
-    def _selection_expression(self, selection):
+    def _resolve_selection(self, selection):
+        """A ``selection=`` argument (True / a name / an expression string / an Expression / a
+        Selection object) as an expression string, or as the Selection when its chain does not
+        fold into one (it holds a lasso, or a drop-na on a host frame)."""
         if selection is True:
             selection = "default"
-        if isinstance(selection, str) and selection in self.selection_expressions:
-            selection = self.selection_expressions[selection]
+        if isinstance(selection, str):
+            selection = self.get_selection(selection) or selection
+        if isinstance(selection, selections.Selection):
+            folded = selection.fold(self)
+            return selection if folded is None else folded
         return str(selection)
 
     def device_keep_mask(self, i1, i2, selection=None, invert=False, cache=False):
         """HBM frame: one device mask of the rows a part takes (filter & selection), or its
         complement (invert: the skip mask of the min/max kernel); None = every row.  cache:
         kept per block like the filter mask (the reference's aggregation parts ask for cached
-        selection masks, cpu.py:548)."""
+        selection masks, cpu.py:548).  A selection that folds into an expression is evaluated
+        with the filter as one device program; one that holds a lasso node by node
+        (``Selection.evaluate_device``), the filter's mask and-ed in after."""
         parts = []
         if self._filter is not None:
             parts.append(f"({self._filter})")
         if selection not in (None, False):
-            parts.append(f"({self._selection_expression(selection)})")
+            selection = self._resolve_selection(selection)
+            if isinstance(selection, selections.Selection):
+                return self._device_selection_mask(selection, i1, i2, invert, cache)
+            parts.append(f"({selection})")
         if not parts:
             return None
         expr = " & ".join(parts)
         expr = f"~({expr})" if invert else expr
         return self._cached_device_mask(expr, i1, i2) if cache else self._eval_device(expr, i1, i2)
 
-    # ---- selections --------------------------------------------------------------
-    def select(self, expression, name="default"):
-        self.selection_expressions[name] = str(expression)
+    def _device_selection_mask(self, selection, i1, i2, invert, cache):
+        from .superutils import mask_combine
 
-    def select_nothing(self, name="default"):
-        self.selection_expressions.pop(name, None)
+        def compute():
+            mask = selection.evaluate_device(self, i1, i2)
+            if self._filter is not None:
+                mask = mask_combine(self.evaluate_filter_mask(i1, i2), mask, "and")
+            return mask_combine(mask, None) if invert else mask
+
+        if not cache:
+            return compute()
+        return self._cached_device_mask(("selection", selection.key(), self._filter, invert), i1, i2, compute)
+
+    def _expression_mask(self, expression, i1, i2, filter_mask=None):
+        """Host frame: a boolean expression over the rows that pass filter_mask, as a bool
+        array; a masked value selects nothing."""
+        mask = self._eval_host(str(expression), i1, i2, filter_mask)
+        if np.ma.isMaskedArray(mask):
+            mask = mask.data & ~np.ma.getmaskarray(mask)
+        return np.asarray(mask, dtype=bool)
+
+    # ---- selections --------------------------------------------------------------
+    @property
+    def selection_expressions(self):
+        """{name: expression} of the current selections whose chain holds only expressions and
+        inversions, folded into one string (``Selection.fold``)."""
+        out = {}
+        for name in self.selection_histories:
+            selection = self.get_selection(name)
+            folded = selection.fold() if selection is not None else None
+            if folded is not None:
+                out[name] = folded
+        return out
+
+    def _selection_dependencies(self):
+        """Every expression a current selection is evaluated from (a lasso's x / y included)."""
+        return [e for name in self.selection_histories if self.get_selection(name) is not None
+                for e in self.get_selection(name).dependencies()]
+
+    def _copy_selections(self, other):
+        self.selection_histories = {k: list(v) for k, v in other.selection_histories.items()}
+        self.selection_history_indices = dict(other.selection_history_indices)
+
+    def get_selection(self, name="default"):
+        """The current Selection object under ``name``, or None."""
+        index = self.selection_history_indices.get(name, -1)
+        return None if index == -1 else self.selection_histories[name][index]
 
     def has_selection(self, name="default"):
-        return name in self.selection_expressions
+        return self.get_selection(name) is not None
+
+    def _selection(self, create_selection, name):
+        """dataframe.py:4937-4951: the new selection is built on the current one and appended
+        after it; what could be redone is dropped.  (After undoing every selection the
+        reference builds on the LAST entry of the history; here on none.)"""
+        history = self.selection_histories.setdefault(name, [])
+        index = self.selection_history_indices.get(name, -1)
+        selection = create_selection(history[index] if index >= 0 else None)
+        del history[index + 1:]
+        history.append(selection)
+        self.selection_history_indices[name] = index + 1
+
+    def selection_undo(self, name="default"):
+        if not self.selection_can_undo(name):
+            raise ValueError(f"selection {name!r} has nothing to undo")
+        self.selection_history_indices[name] -= 1
+
+    def selection_redo(self, name="default"):
+        if not self.selection_can_redo(name):
+            raise ValueError(f"selection {name!r} has nothing to redo")
+        self.selection_history_indices[name] += 1
+
+    def selection_can_undo(self, name="default"):
+        return self.selection_history_indices.get(name, -1) > -1
+
+    def selection_can_redo(self, name="default"):
+        return self.selection_history_indices.get(name, -1) + 1 < len(self.selection_histories.get(name, []))
+
+    def select(self, boolean_expression, mode="replace", name="default"):
+        """dataframe.py:4712-4730: select the rows where the boolean expression holds, combined
+        with the current selection under ``name`` by ``mode`` (replace / and / or / xor /
+        subtract).  Selections are recorded per name (``selection_undo`` / ``selection_redo``).
+        ``None`` clears the selection; it is not recorded when there is none to clear."""
+        selections._check_mode(mode)
+        boolean_expression = _ensure_string(boolean_expression)
+        if boolean_expression is None and not self.has_selection(name):
+            return
+
+        def create(current):
+            return selections.SelectionExpression(boolean_expression, current, mode) if boolean_expression else None
+        self._selection(create, name)
+
+    def select_nothing(self, name="default"):
+        self.select(None, name=name)
+
+    def select_inverse(self, name="default"):
+        """Select what is not selected (ValueError when nothing is)."""
+        self._selection(selections.SelectionInvert, name)
+
+    def select_non_missing(self, drop_nan=True, drop_masked=True, column_names=None, mode="replace", name="default"):
+        """dataframe.py:4732-4748: the rows without a NaN (float columns) / masked value in any
+        of ``column_names`` (default: every real column)."""
+        column_names = _ensure_strings(list(column_names or self.columns))
+        self._selection(lambda current: selections.SelectionDropNa(drop_nan, drop_masked, column_names, current, mode),
+                        name)
+
+    def select_rectangle(self, x, y, limits, mode="replace", name="default"):
+        """dataframe.py:4794-4806: ``select_box([x, y], [(x1, x2), (y1, y2)])``."""
+        self.select_box([x, y], limits, mode=mode, name=name)
+
+    def select_box(self, spaces, limits, mode="replace", name="default"):
+        """dataframe.py:4808-4825: the n-dimensional box ``[(x1, x2), (y1, y2), ...]``, both ends
+        included.  As in the reference the limits enter the expression through ``%f``: six
+        digits after the point, so a limit is rounded to 1e-6 and one beyond about 1e15 loses
+        its low digits."""
+        sorted_limits = [(min(l), max(l)) for l in limits]
+        expressions = ["((%s) >= %f) & ((%s) <= %f)" % (expression, lmin, expression, lmax) for
+                       (expression, (lmin, lmax)) in zip(_ensure_strings(list(spaces)), sorted_limits)]
+        self.select("&".join(expressions), mode=mode, name=name)
+
+    def select_circle(self, x, y, xc, yc, r, mode="replace", name="default", inclusive=True):
+        """dataframe.py:4827-4851: ``(x - xc)**2 + (y - yc)**2 <= r**2`` (``<`` when not
+        inclusive); the constants enter with ``repr()`` and so keep every bit."""
+        x, y = _ensure_string(x), _ensure_string(y)
+        xc, yc, r2 = repr(float(xc)), repr(float(yc)), repr(float(r) ** 2)
+        op = "<=" if inclusive else "<"
+        self.select(f"((({x}) - {xc}) ** 2 + (({y}) - {yc}) ** 2) {op} {r2}", mode=mode, name=name)
+
+    def select_ellipse(self, x, y, xc, yc, width, height, angle=0, mode="replace", name="default", radians=False,
+                       inclusive=True):
+        """dataframe.py:4853-4894: the ellipse centred on (xc, yc) with the diameters width and
+        height, turned by ``angle`` (degrees unless ``radians``; the reference leaves the angle
+        undefined for ``radians=True``).  Constants enter with ``repr()``."""
+        x, y = _ensure_string(x), _ensure_string(y)
+        alpha = float(angle) if radians else float(np.deg2rad(angle))
+        xr, yr = width / 2, height / 2
+        r = max(xr, yr)
+        a2, b2, r2 = repr(float((xr / r) ** 2)), repr(float((yr / r) ** 2)), repr(float(r) ** 2)
+        cos, sin = repr(float(np.cos(alpha))), repr(float(np.sin(alpha)))
+        dx, dy = f"(({x}) - {float(xc)!r})", f"(({y}) - {float(yc)!r})"
+        op = "<=" if inclusive else "<"
+        self.select(f"(({dx} * {cos} + {dy} * {sin}) ** 2 / {a2} + ({dx} * {sin} - {dy} * {cos}) ** 2 / {b2}) {op} {r2}",
+                    mode=mode, name=name)
+
+    def select_lasso(self, expression_x, expression_y, xsequence, ysequence, mode="replace", name="default"):
+        """dataframe.py:4896-4911: the rows whose (x, y) lies inside the polygon with the
+        vertices (xsequence[k], ysequence[k]), the reference's pnpoly test.  On an HBM frame it
+        runs as one kernel over the two columns; only the vertices go to the device."""
+        expression_x, expression_y = _ensure_string(expression_x), _ensure_string(expression_y)
+        self._selection(lambda current: selections.SelectionLasso(expression_x, expression_y, xsequence, ysequence,
+                                                                  current, mode), name)
+
+    def set_selection(self, selection, name="default"):
+        """Make the Selection object the current selection under ``name``."""
+        self._selection(lambda current: selection, name)
+
+    def selected_length(self, selection="default"):
+        """The number of selected rows (dataframe.py:6612-6614)."""
+        return int(np.asarray(self.count(selection=selection)).item())
 
     def evaluate_selection_mask(self, selection, i1=0, i2=None, filter_mask=None, cache=False):
         i2 = self._length if i2 is None else i2
         if isinstance(filter_mask, DeviceArray) or (filter_mask is None and self.is_device_resident()):
             # HBM frame: the device mask of (filter &) selection over the whole chunk
             return self.device_keep_mask(i1, i2, selection, cache=cache)
-        selection = self._selection_expression(selection)
-        mask = self._eval_host(str(selection), i1, i2, filter_mask)
-        if np.ma.isMaskedArray(mask):
-            mask = mask.data & ~np.ma.getmaskarray(mask)
-        return np.asarray(mask, dtype=bool)
+        selection = self._resolve_selection(selection)
+        if isinstance(selection, selections.Selection):
+            return selection.evaluate(self, i1, i2, filter_mask)
+        return self._expression_mask(selection, i1, i2, filter_mask)
 
     # ---- execution ---------------------------------------------------------------
     def execute(self):

@@ -286,3 +286,44 @@ def cov_finish(values, N):
         moments2 = sums / counts
     with np.errstate(invalid="ignore"):  # inf - inf in a cell holding an infinite value
         return moments2 - meansxy
+
+
+def lasso_bounds(vertx, verty):
+    """(meanx, meany, radius) of a lasso as SelectionLasso.evaluate computes them
+    (selections.py:182-185): the vertex mean and the largest vertex distance from it; NaN for
+    an empty lasso (nothing is inside it)."""
+    vertx, verty = np.asarray(vertx, dtype=np.float64), np.asarray(verty, dtype=np.float64)
+    if len(vertx) == 0:
+        return float("nan"), float("nan"), float("nan")
+    meanx, meany = vertx.mean(), verty.mean()
+    with np.errstate(all="ignore"):
+        radius = np.sqrt((meanx - vertx) ** 2 + (meany - verty) ** 2).max()
+    return float(meanx), float(meany), float(radius)
+
+
+def pnpoly(x, y, vertx, verty, meanx, meany, radius):
+    """vaexfast.pnpoly (vaexfast.cpp:1757-1775) for host columns: the boolean mask of the points
+    (x[k], y[k]) inside the polygon, the C loop's float64 arithmetic operation for operation.
+    The loop runs over the edges, vectorised over the rows inside the radius, of which each
+    edge touches only those whose y it straddles; row ranges are split over the host threads."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    vertx, verty = np.asarray(vertx, dtype=np.float64), np.asarray(verty, dtype=np.float64)
+    meanx, meany, r2 = np.float64(meanx), np.float64(meany), np.float64(radius) * np.float64(radius)
+    nvert = len(vertx)
+    out = np.zeros(len(x), dtype=bool)
+
+    def part(i0, i1):
+        with np.errstate(all="ignore"):
+            tx, ty = x[i0:i1], y[i0:i1]
+            rows = np.flatnonzero((tx - meanx) * (tx - meanx) + (ty - meany) * (ty - meany) < r2)
+            tx, ty = tx[rows], ty[rows]
+            c = np.zeros(len(rows), dtype=bool)
+            for i in range(nvert):
+                j = i - 1 if i else nvert - 1
+                k = np.flatnonzero((verty[i] > ty) != (verty[j] > ty))
+                if len(k):
+                    c[k] ^= tx[k] < (vertx[j] - vertx[i]) * (ty[k] - verty[i]) / (verty[j] - verty[i]) + vertx[i]
+            out[i0:i1][rows] = c
+
+    _run(part, len(x), min_split=1 << 16)
+    return out

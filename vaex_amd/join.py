@@ -122,7 +122,7 @@ def _like(df, columns):
     new.variables = dict(df.variables)
     new.virtual_columns = dict(df.virtual_columns)
     new._categories = dict(df._categories)
-    new.selection_expressions = dict(df.selection_expressions)
+    new._copy_selections(df)
     new._filter = df._filter
     if not columns:
         new._length = 0
@@ -180,8 +180,9 @@ def _rename(df, old, new):
     virtual column, filter or selection that uses the old name raises."""
     if old == new:
         return
-    users = [e for e in list(df.virtual_columns.values()) + list(df.selection_expressions.values()) + [df._filter]
-             if e is not None and _uses(e, old)]
+    # _selection_dependencies: also the x / y expressions of a lasso, which has no folded string
+    users = [e for e in list(df.virtual_columns.values()) + list(df.selection_expressions.values())
+             + df._selection_dependencies() + [df._filter] if e is not None and _uses(e, old)]
     if users:
         raise NotImplementedError(
             f"join renames column {old!r} to {new!r}, but the expression {users[0]!r} uses it: expression rewriting "

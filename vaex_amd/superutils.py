@@ -476,6 +476,77 @@ def index_matched(lookup):
     return rows[:m.value], out[:m.value]
 
 
+# edges of a lasso a workgroup stages in LDS at a time (select.hip PP_CHUNK) and the rows a
+# workgroup takes per step (PP_TILE: 256 lanes of 8 rows)
+PNPOLY_LDS_EDGES = 512
+PNPOLY_WG_ROWS = 2048
+
+
+def _device_mask(a):
+    """A mask as a DeviceArray of bytes (a host mask is staged)."""
+    if isinstance(a, DeviceArray):
+        if a.dtype.itemsize != 1:
+            raise TypeError("a mask holds one byte per row")
+        return a
+    return DeviceArray.from_numpy(np.ascontiguousarray(a).view(np.uint8) if np.asarray(a).dtype == np.bool_
+                                  else np.ascontiguousarray(a, dtype=np.uint8))
+
+
+def pnpoly(x, y, xseq, yseq, prev=None, mode="replace"):
+    """The lasso: ``mode(prev == 1, inside(x, y))`` for the polygon with the vertices
+    (xseq[k], yseq[k]), ``inside`` being vaexfast.pnpoly (vaexfast.cpp:1757-1775) with the
+    mean / radius pre-test of SelectionLasso.evaluate (selections.py:182-185).  DeviceArray
+    columns (float64 / float32, each its own dtype; a mixed pair stages the host one) go to the
+    kernel (``vh_pnpoly``) and give a DeviceArray of bool: only the vertices cross to the
+    device, nothing comes back.  NumPy columns take the host path (``hostops.pnpoly``) and give
+    a bool array.  ``prev``: a mask of which only bytes equal to 1 count; without it, and / or /
+    xor give the new mask and subtract its complement.  An empty polygon holds no point."""
+    from . import hostops
+    from .selections import _select_functions
+    if mode not in _lib.SELECT_MODE:
+        raise ValueError(f"unknown selection mode {mode!r}")
+    vx = np.ascontiguousarray(xseq, dtype=np.float64)
+    vy = np.ascontiguousarray(yseq, dtype=np.float64)
+    if vx.ndim != 1 or vx.shape != vy.shape:
+        raise ValueError("xseq and yseq must be two sequences of equal length")
+    if len(x) != len(y) or (prev is not None and len(prev) != len(x)):
+        raise ValueError("x, y and prev differ in length")
+    meanx, meany, radius = hostops.lasso_bounds(vx, vy)
+    if not isinstance(x, DeviceArray) and not isinstance(y, DeviceArray):
+        mask = hostops.pnpoly(x, y, vx, vy, meanx, meany, radius)
+        if prev is not None:
+            prev = prev.to_numpy() if isinstance(prev, DeviceArray) else np.asarray(prev)
+            prev = prev.view(np.uint8) == 1 if prev.dtype == np.bool_ else prev == 1
+        return _select_functions[mode](prev, mask)
+    cols = []
+    for c in (x, y):
+        if not isinstance(c, DeviceArray):
+            c = np.asarray(c)
+            c = DeviceArray.from_numpy(c if c.dtype == np.float32 else c.astype(np.float64))
+        if c.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise TypeError(f"pnpoly takes float64 / float32 columns, not {c.dtype}")
+        cols.append(c)
+    pkeep = None if prev is None else _device_mask(prev)
+    out = DeviceArray(len(x), np.bool_)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _lib.call("vh_pnpoly", cols[0].ptr, _lib.dtype_code(cols[0].dtype)[0], cols[1].ptr, _lib.dtype_code(cols[1].dtype)[0],
+              len(x), vx.ctypes.data_as(dp), vy.ctypes.data_as(dp), len(vx), meanx, meany, radius,
+              None if pkeep is None else pkeep.ptr, _lib.SELECT_MODE[mode], out.ptr)
+    return out
+
+
+def mask_combine(a, b=None, mode="and"):
+    """``mode(a == 1, b == 1)`` of two device masks as a new DeviceArray of bool
+    (``vh_mask_combine``); ``b`` None: the complement of ``a``."""
+    a = _device_mask(a)
+    bkeep = None if b is None else _device_mask(b)
+    if bkeep is not None and len(bkeep) != len(a):
+        raise ValueError("masks differ in length")
+    out = DeviceArray(len(a), np.bool_)
+    _lib.call("vh_mask_combine", a.ptr, None if bkeep is None else bkeep.ptr, _lib.SELECT_MODE[mode], len(a), out.ptr)
+    return out
+
+
 def _register():
     ns = globals()
     for dtype in DTYPES:
