@@ -119,7 +119,10 @@ int vh_stream(void **stream);
  * that missed their pass-A region and took global atomics), "hashagg_overflow_rows",
  * "set_overflow_rows" (the groupby / ordered_set partition overflow paths); the maximum since
  * the last reset, every device: "tile_stream_rounds" (rounds of the longest segment walk of a
- * tile path pass-B unit in the stream layout, counted on the host from the planned units) */
+ * tile path pass-B unit in the stream layout, counted on the host from the planned units);
+ * host images (vh_agg_set_host_image), every device, host counts: "host_image_bins" (bins
+ * that left at least one registered image current), "host_image_tile_units" (the most pass-B
+ * units that shared one tile's ticket in a mirrored launch: a maximum) */
 int vh_stat_read(const char *name, uint64_t *value, int reset);
 
 /* ---- Binners: superagg_binners.cpp ------------------------------------- */
@@ -185,6 +188,18 @@ int vh_agg_info(const vh_agg *agg, uint64_t *bytes, int *grid_dtype, uint64_t *i
 int vh_agg_download(vh_agg *agg, void *host, uint64_t bytes);
 int vh_agg_upload(vh_agg *agg, const void *host, uint64_t bytes);
 int vh_agg_download_order(vh_agg *agg, void *host, uint64_t bytes); /* AggFirst order grid */
+/* (new) Registers `host` as the aggregator's host image: page-locked, mapped memory (vh_host_alloc,
+ * hipHostMalloc), 16-byte aligned, bytes == length1d * itemsize and >= 256 KiB; host == NULL
+ * clears the registration.  VH_ERR_ARG for anything else (pageable memory included) and for an
+ * AggCov.  While an image is registered, a vh_grid_bin of count / sum / sum-moment aggregators
+ * over device columns that takes the tiled engine writes every finished tile of the grid into
+ * the image from inside its last kernel, and vh_agg_download(agg, host, bytes) into that same
+ * image is then a stream synchronize and no copy.  Every other write of the device grid (a bin
+ * on another route, vh_agg_upload, vh_agg_reduce, vh_comm_agg_allreduce) leaves the image stale
+ * and the next download an ordinary copy; vh_agg_device_ptr drops the registration.  The memory must stay valid until
+ * the registration is cleared, replaced or dropped, or the aggregator destroyed: each of those
+ * waits for the library stream first.  VH_HOST_IMAGE=0 (read per bin) turns the mirror off. */
+int vh_agg_set_host_image(vh_agg *agg, void *host, uint64_t bytes);
 /* Nonzero cells of grid items [begin, end): out3 = {count, first index, last index} relative to
  * begin ({0, -1, -1} when none) -- the occupied range of a dense groupby's count(*) grid, found
  * on the device (groupby.py:484-533 keeps the cells with count > 0). */

@@ -76,6 +76,7 @@ SIGNATURES = {
     "vh_agg_download": (_i32, [_vp, _vp, _u64]),
     "vh_agg_upload": (_i32, [_vp, _vp, _u64]),
     "vh_agg_download_order": (_i32, [_vp, _vp, _u64]),
+    "vh_agg_set_host_image": (_i32, [_vp, _vp, _u64]),
     "vh_agg_occupancy": (_i32, [_vp, _u64, _u64, _vp]),
     "vh_agg_percentile": (_i32, [_vp, _vp, _i32, _dbl, _dbl, _vp, _u64]),
     "vh_agg_mutual_information": (_i32, [_vp, _vp, _u64]),

@@ -1500,6 +1500,11 @@ int vh_agg_download(vh_agg *a, void *host, uint64_t bytes) {
         return VH_OK;
     }
     if (bytes != a->grid->length1d * a->grid_isz) fail(VH_ERR_ARG, "download size mismatch");
+    if (host && host == a->image && a->image_current) {
+        // the last bin's pass B mirrored every cell into this image: wait for it, copy nothing
+        VH_HIP(hipStreamSynchronize(stream()));
+        return VH_OK;
+    }
     nunique_finalize(a);
     if (bytes <= (1u << 20)) {
         // small grids through a page-locked block: a pageable read-back is a staged copy
@@ -1512,6 +1517,29 @@ int vh_agg_download(vh_agg *a, void *host, uint64_t bytes) {
         copy_to_host(host, a->g.ptr, bytes, stream());
         VH_HIP(hipStreamSynchronize(stream()));
     }
+    VH_API_END
+}
+
+int vh_agg_set_host_image(vh_agg *a, void *host, uint64_t bytes) {
+    VH_API_BEGIN
+    std::lock_guard<std::mutex> lk(a->grid->mu);
+    // a pass B that mirrors into the old image may still be queued: it ends before the caller
+    // may reuse or free that memory (and before a new image takes its place)
+    if (a->image) VH_HIP(hipStreamSynchronize(stream()));
+    a->image = a->image_dev = nullptr;
+    a->image_current = false;
+    if (!host) return VH_OK;
+    if (a->kind == VH_AGG_COV) fail(VH_ERR_ARG, "host image: AggCov grids are expanded when read, not mirrored");
+    if (bytes != a->grid->length1d * a->grid_isz) fail(VH_ERR_ARG, "host image size mismatch");
+    if (bytes < (256u << 10)) fail(VH_ERR_ARG, "host image below 256 KiB");
+    if (reinterpret_cast<uintptr_t>(host) & 15) fail(VH_ERR_ARG, "host image not 16-byte aligned");
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, host) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer) {
+        (void)hipGetLastError();
+        fail(VH_ERR_ARG, "host image is not page-locked, mapped memory");
+    }
+    a->image = host;
+    a->image_dev = at.devicePointer;
     VH_API_END
 }
 
@@ -1588,6 +1616,7 @@ int vh_agg_upload(vh_agg *a, const void *host, uint64_t bytes) {
     }
     if (bytes != a->grid->length1d * a->grid_isz) fail(VH_ERR_ARG, "upload size mismatch");
     if (a->kind == VH_AGG_NUNIQUE) return VH_OK;  // a derived grid (recomputed when read)
+    a->image_current = false;
     VH_HIP(hipMemcpyAsync(a->g.ptr, host, bytes, hipMemcpyHostToDevice, stream()));
     VH_HIP(hipStreamSynchronize(stream()));
     VH_API_END
@@ -1598,6 +1627,10 @@ int vh_agg_device_ptr(vh_agg *a, void **grid_dptr, void **grid2_dptr) {
     std::lock_guard<std::mutex> lk(a->grid->mu);
     nunique_finalize(a);
     VH_HIP(hipStreamSynchronize(stream()));  // the grid's fills and bins are done for any stream
+    // the address goes to writers the library cannot see (the all-reduce): the host image is
+    // dropped, so every later read-back is the ordinary copy (no mirror is in flight: synced)
+    a->image = a->image_dev = nullptr;
+    a->image_current = false;
     if (grid_dptr) *grid_dptr = a->g.ptr;
     if (grid2_dptr) *grid2_dptr = a->g2.ptr;
     VH_API_END
@@ -1607,6 +1640,7 @@ int vh_agg_reduce(vh_agg *a, vh_agg *const *others, int nothers) {
     VH_API_BEGIN
     std::lock_guard<std::mutex> lk(a->grid->mu);
     const uint64_t L = a->grid->length1d;
+    if (nothers > 0) a->image_current = false;  // the merge writes the device grid only
     for (int k = 0; k < nothers; k++) {
         vh_agg *o = others[k];
         if (o->kind != a->kind || o->dtype != a->dtype || o->grid->length1d != L ||
@@ -1683,7 +1717,29 @@ int vh_grid_bin(vh_grid *g, vh_agg *const *aggs, int naggs, uint64_t length, int
         if (a->mask.set) check_column(a->mask, length, "aggregator mask");
     }
     if (length == 0 || naggs == 0) return VH_OK;
+    // Host images: whatever route this bin takes writes the device grids, so no image stays
+    // current; the aggregators whose cells are final at pass B's flush (counts, sums and sum
+    // moments: 8-byte cells) offer theirs to the tiled engine, and those it reports as written
+    // in full are current again.  (Min / max are merged after pass B, first / nunique / cov
+    // have their own finishers: never offered, never current.)
+    std::vector<vh::HostImageReq> &images = g->ws.images;
+    images.clear();
+    for (int k = 0; k < naggs; k++) {
+        vh_agg *a = aggs[k];
+        a->image_current = false;
+        const bool mirrored = a->kind == VH_AGG_COUNT || a->kind == VH_AGG_SUM || a->kind == VH_AGG_SUM_MOMENT;
+        if (a->image_dev && mirrored && a->grid_isz == 8) images.push_back({a->g.ptr, a->image, a->image_dev, false});
+    }
+    struct Clear {  // also when a route fails
+        std::vector<vh::HostImageReq> &v;
+        ~Clear() { v.clear(); }
+    } clear_images{images};
     run_bin(g, aggs, naggs, length);
+    bool any = false;
+    for (int k = 0; k < naggs; k++)
+        for (const vh::HostImageReq &r : images)
+            if (r.grid == aggs[k]->g.ptr && r.image_dev == aggs[k]->image_dev && r.written) aggs[k]->image_current = any = true;
+    if (any) note_host_image_bin();
     VH_API_END
 }
 
@@ -1766,6 +1822,9 @@ void run_bin(vh_grid *g, vh_agg *const *aggs, int naggs, uint64_t length) {
         note(aggs[k]->mask);
         for (const ColumnRef &c : aggs[k]->cols) note(c);
     }
+    // host columns are binned in chunks: each would mirror its image again, only the last one
+    // for use (the tiled routes below take device columns as one chunk)
+    if (any_host) g->ws.images.clear();
     const uint64_t L = g->length1d;
     // count / sum of other native dtypes without masks on grids beyond the LDS sub-grid size
     // (any number of them: run in groups of at most MAX_FUSED_AGGS with at most two sums, one

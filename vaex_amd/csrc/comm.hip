@@ -407,6 +407,7 @@ int vh_comm_agg_allreduce(vh_comm *c, vh_agg *a) {
     std::lock_guard<std::mutex> lk(c->mu);
     std::lock_guard<std::mutex> glk(a->grid->mu);
     const uint64_t L = a->grid->length1d;
+    a->image_current = false;  // the all-reduce rewrites the device grid only: the next read-back is the copy
     switch (a->kind) {
     case VH_AGG_COUNT: case VH_AGG_SUM: case VH_AGG_SUM_MOMENT:
         comm_allreduce_dev(c, a->g.ptr, L, a->grid_dtype, VH_OP_SUM);

@@ -181,8 +181,21 @@ struct HostPipe {
     int find(const void *ptr) const;
 };
 
+// A registered host image (vh_agg_set_host_image) offered to the bin in progress: the tiled
+// engine's pass B mirrors `grid`'s finished tiles into `image_dev` and sets `written` when the
+// bin wrote every byte of the image (tiled.hip)
+struct HostImageReq {
+    void *grid;       // the aggregator's device grid (the key: FusedAgg::grid)
+    void *image;      // the page-locked image, length1d * 8 bytes
+    void *image_dev;  // its device-side address
+    bool written;
+};
+
 // per-grid device scratch, reused across bin() calls
 struct Workspace {
+    // images of the aggregators of the vh_grid_bin in progress (empty: mirror nothing); only a
+    // bin that runs as one chunk of device columns offers them
+    std::vector<HostImageReq> images;
     DevBuf idx;                                   // generic path indices1d
     DevBuf cells;                                 // small-grid path: u16 cell per row
     DevBuf first_part;                            // small-grid AggFirst: per-workgroup (key, row) partials
@@ -202,6 +215,11 @@ uint64_t stat_hashagg_overflow(bool reset);
 uint64_t stat_set_overflow(bool reset);
 // the most rounds a pass-B unit of a stream-layout launch walked (tile_plan.hpp: unit_rounds)
 uint64_t stat_tile_stream_rounds(bool reset);
+// host-image mirror: bins that left an aggregator's registered image current, and the most
+// pass-B units that shared one tile's ticket in a mirrored launch (host counts, no kernel part)
+uint64_t stat_host_image_bins(bool reset);
+uint64_t stat_host_image_tile_units(bool reset);
+void note_host_image_bin();
 // AggFirst over a grid too large for LDS through the tile-partitioned exchange (first.hip):
 // fills the aggregator's s_key / s_row scratch for rows [0, n) of this chunk (global rows
 // row0 + j); false when not eligible or when its resolve list overflowed (scratch reset)
@@ -242,6 +260,13 @@ struct vh_agg {
     uint64_t L = 0;        // grid length1d
     uint64_t nu_n = 0;
     vh::DevBuf nu_cell, nu_val;
+    // the registered host image (vh_agg_set_host_image): page-locked, mapped, 16-byte aligned,
+    // of the grid's size; image_dev its device-side address.  image_current: the last write of
+    // the device grid was a bin whose pass B mirrored every cell into the image, so
+    // vh_agg_download into `image` is a stream synchronize; anything else that can write the
+    // grid clears it
+    void *image = nullptr, *image_dev = nullptr;
+    bool image_current = false;
 };
 
 namespace vh {

@@ -808,6 +808,8 @@ int vh_stat_read(const char *name, uint64_t *value, int reset) {
     const std::string n = name ? name : "";
     if (n == "tile_overflow_rows") *value = stat_tile_overflow(reset != 0);
     else if (n == "tile_stream_rounds") *value = stat_tile_stream_rounds(reset != 0);
+    else if (n == "host_image_bins") *value = stat_host_image_bins(reset != 0);
+    else if (n == "host_image_tile_units") *value = stat_host_image_tile_units(reset != 0);
     else if (n == "hashagg_overflow_rows") *value = stat_hashagg_overflow(reset != 0);
     else if (n == "set_overflow_rows") *value = stat_set_overflow(reset != 0);
     else if (n == "first_tiled_chunks") *value = stat_first_tiled(reset != 0);

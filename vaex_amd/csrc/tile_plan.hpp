@@ -160,6 +160,14 @@ struct TileParams {
     // one keep mask shared by every aggregator (a selection or filter; 1 = keep) applied by the
     // fast pass A per row: masked rows are dropped before the exchange (MK instantiations)
     const uint8_t *rowmask;
+    // host-image mirror (pass B's epilogue): image[k] is the device-side address of aggregator
+    // k's registered page-locked host image, null when it is not mirrored.  Every unit of tile
+    // t draws a ticket from tickets[t] (zeroed per launch) after its flush; the unit that draws
+    // tile_units[t] - 1 is the tile's last and copies the tile's finished cells from the device
+    // grid to the images.  tickets null: no aggregator of the launch is mirrored
+    void *image[MAX_FUSED_AGGS];
+    uint32_t *tickets;           // [T]
+    const uint32_t *tile_units;  // [T] units planned for the tile
 };
 
 // The VH_TILE_* environment switches (A/B runs), read on every call by tiled.hip
@@ -168,6 +176,7 @@ struct TileSwitches {
     // mixed / integer fast kernels; NARROW, 4-byte value slots; STREAM, the stream layout; PACK, two
     // narrow slots in one array
     bool rowmask = true, f32 = true, narrow = true, stream = true, pack = true;
+    bool host_image = true;  // VH_HOST_IMAGE=0: pass B mirrors no tile into a registered host image
     uint32_t wide = 7;    // VH_TILE_WIDE: bit 0 wide stream-out, bit 1 / 2 non-temporal cell / value stores
     uint64_t wgpad = 0;   // VH_TILE_WGPAD: extra entries between the workgroups' streams
     uint32_t debug = 0;   // VH_TILE_DEBUG (ablation build only)
@@ -477,7 +486,11 @@ struct MetaLayout {  // byte offsets into the meta buffer; [T] arrays unless not
     uint64_t hist;    // [2][T]: rows, and squared per-block rows
     uint64_t toff, sstart, scap, sfill, cap;
     uint64_t fills, units, brange;  // [T][W], [max_units] WorkUnit, [SAMPLE_BLOCKS][2]
-    uint64_t bytes;
+    uint64_t bytes;                 // end of the arrays above
+    // the host-image mirror's arrays follow them (TileParams::tickets, tile_units), so the
+    // offsets above are what they were without the mirror; alloc: the buffer's size
+    uint64_t tickets, tunits;
+    uint64_t alloc;
 };
 struct TileLaunch {
     uint32_t W = 0;                             // pass-A workgroups
@@ -523,6 +536,10 @@ inline TileLaunch plan_launch(const TilePlan &pl, uint64_t n, int cus, int block
     m.units = take(sizeof(WorkUnit) * L.max_units);
     m.brange = take(8 * (uint64_t)SAMPLE_BLOCKS);
     m.bytes = o;
+    o = (o + 15) & ~uint64_t(15);
+    m.tickets = take(4 * (uint64_t)T);
+    m.tunits = take(4 * (uint64_t)T);
+    m.alloc = o;
     return L;
 }
 
@@ -651,6 +668,54 @@ inline void plan_units(const TilePlan &pl, const TileLaunch &L, uint64_t n, int 
         units.swap(sorted);
     }
     if (units.size() > L.max_units) fail(VH_ERR_RUNTIME, "tiled binning: work-unit table overflow");
+}
+
+// Host-image mirror: the units planned per tile (TileParams::tile_units; the unit that draws
+// ticket counts[t] - 1 is tile t's last and copies the tile to the images).  Returns the most
+// units on one tile.  A tile without a unit is never mirrored by the kernel: the caller copies
+// its cells itself (mirror_uncovered)
+inline uint32_t count_tile_units(const std::vector<WorkUnit> &units, uint32_t T, std::vector<uint32_t> &counts) {
+    counts.assign(T, 0);
+    uint32_t most = 0;
+    for (const WorkUnit &u : units)
+        if (u.tile < T) most = std::max(most, ++counts[u.tile]);
+    return most;
+}
+// Launch order of a mirrored pass B.  plan_units puts the largest units first, so the coldest
+// tiles' units end the launch and their tiles all complete in its last microseconds: their
+// mirrors (64 KB per tile of a count + sum plan, ~7 MB for the ~110 cold tiles of C2) then
+// queue on the 52 GB/s host link when the reduce work is over (+0.13 ms of pass B, DESIGN
+// §5.21).  The units of tiles whose units hold fewer than 1 / MIRROR_COLD_DIV of the split
+// target (n / 4 cus rows) go first instead, where the link is idle; their reduce work is too
+// small to have balanced the tail, which keeps every other unit in plan_units' order.  The
+// units themselves, and so the results, are what plan_units returned.
+constexpr double MIRROR_COLD_DIV = 64;
+inline void mirror_order_units(uint64_t n, int cus, const uint64_t *hist, uint64_t sampled, const std::vector<uint32_t> &counts,
+                               std::vector<WorkUnit> &units) {
+    const double target = std::max(1.0, (double)n / ((double)cus * 4));
+    std::stable_partition(units.begin(), units.end(), [&](const WorkUnit &u) {
+        const double e = (double)n * (double)hist[u.tile] / (double)sampled;
+        return e / (double)std::max<uint32_t>(counts[u.tile], 1) < target / MIRROR_COLD_DIV;
+    });
+}
+// cells [first, first + n) of tile t: every cell of the grid lies in exactly one tile
+inline void tile_cells(const TileParams &tp, uint32_t t, uint64_t &first, uint64_t &n) {
+    first = (uint64_t)t << tp.s_log2;
+    n = first < tp.cells ? std::min<uint64_t>((uint64_t)1 << tp.s_log2, tp.cells - first) : 0;
+}
+// maximal runs [first, first + n) of cells whose tiles no unit covers, in grid order
+struct CellRange { uint64_t first, n; };
+inline std::vector<CellRange> mirror_uncovered(const TileParams &tp, const std::vector<uint32_t> &counts) {
+    std::vector<CellRange> out;
+    for (uint32_t t = 0; t < tp.ntiles; t++) {
+        if (counts[t]) continue;
+        uint64_t first, n;
+        tile_cells(tp, t, first, n);
+        if (!n) continue;
+        if (!out.empty() && out.back().first + out.back().n == first) out.back().n += n;
+        else out.push_back({first, n});
+    }
+    return out;
 }
 
 // Rounds of pass B's segment walk over one work unit (k_tile_reduce: its `rounds`).  Stream layout:

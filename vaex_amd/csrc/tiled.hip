@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cmath>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1497,6 +1498,50 @@ template <int NV, bool X = false> struct TileRun {
     }
 };
 
+// Pass B's epilogue for registered host images (TileParams::image): a tile's cells are final
+// once its last unit has flushed, so that unit copies them from the device grid -- which also
+// holds earlier bins, pass A's overflow atomics and the other units' adds -- to the images while
+// the rest of pass B still runs; the read-back of the grids then needs no kernel of its own.
+// Every unit of the tile calls this once, after its flush (or instead of it when it holds no
+// entries); no workgroup waits for another.  The hand-off is the counter form: every wave
+// drains its flush atomics, one barrier, lane 0 releases at agent scope and draws the tile's
+// ticket; the workgroup that draws the last one acquires once and tells its other waves
+// through the first word of the LDS tile (free by then).  `lds`: at least 4 bytes.
+__device__ __forceinline__ void tile_mirror(const FusedAggs &fa, const TileParams &tp, uint32_t t, unsigned char *lds,
+                                            uint32_t nthreads) {
+    if (!tp.tickets) return;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    volatile uint32_t *s_last = reinterpret_cast<volatile uint32_t *>(lds);
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t drawn = __hip_atomic_fetch_add(tp.tickets + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool last = drawn + 1 == tp.tile_units[t];
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        *s_last = last ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!*s_last) return;
+    // mirrored grids have 8-byte cells; a tile starts at a multiple of 16 bytes
+    const uint64_t c0 = (uint64_t)t << tp.s_log2;
+    const uint32_t ncell = (uint32_t)min((uint64_t)1 << tp.s_log2, tp.cells - c0);
+    const uint32_t nvec = ncell >> 1;
+#pragma unroll
+    for (int k = 0; k < MAX_FUSED_AGGS; k++) {
+        if (k >= fa.na) break;
+        if (!tp.image[k]) continue;
+        const uint4 *src = reinterpret_cast<const uint4 *>(static_cast<const uint64_t *>(fa.a[k].grid) + c0);
+        uint4 *dst = reinterpret_cast<uint4 *>(static_cast<uint64_t *>(tp.image[k]) + c0);
+        for (uint32_t i = threadIdx.x; i < nvec; i += nthreads) dst[i] = src[i];
+        if ((ncell & 1) && threadIdx.x == 0)  // the grid's last cell when its count is odd
+            static_cast<uint64_t *>(tp.image[k])[c0 + ncell - 1] = static_cast<const uint64_t *>(fa.a[k].grid)[c0 + ncell - 1];
+    }
+}
+
 constexpr int TB_UNROLL = 8;
 #ifndef VH_TB_VU
 #define VH_TB_VU 0  // 8-entry chunks per lane per step (0 = by NV)
@@ -1632,7 +1677,10 @@ __global__ __launch_bounds__(TBT) void k_tile_reduce(FusedAggs fa, TileParams tp
     } else {
         any0 = load_round();
     }
-    if (!__syncthreads_or(any0 || (stream && rounds > 1))) return;
+    if (!__syncthreads_or(any0 || (stream && rounds > 1))) {  // no entries: nothing to flush
+        tile_mirror(fa, tp, t, lds_raw, TBT);
+        return;
+    }
     uint32_t *lw = reinterpret_cast<uint32_t *>(lds_raw);
     for (uint32_t i = threadIdx.x; i < fa.lds_words; i += TBT) lw[i] = 0;
     if (!tp.flags_mode && !stream) scan_round();
@@ -2020,6 +2068,7 @@ __global__ __launch_bounds__(TBT) void k_tile_reduce(FusedAggs fa, TileParams tp
             }
         }
     }
+    tile_mirror(fa, tp, t, lds_raw, TBT);
 }
 
 // ---- the kernels behind the planner's descriptors: the only place that names pass-A and pass-B
@@ -2141,6 +2190,7 @@ static TileSwitches read_switches() {
     sw.narrow = !off("VH_TILE_NARROW");
     sw.stream = !off("VH_TILE_STREAM");
     sw.pack = !off("VH_TILE_PACK");
+    sw.host_image = !off("VH_HOST_IMAGE");
     if (const char *e = getenv("VH_TILE_WIDE")) sw.wide = (uint32_t)atoi(e);
     if (const char *e = getenv("VH_TILE_WGPAD")) sw.wgpad = (uint64_t)strtoull(e, nullptr, 10);
 #ifdef VH_ABLATION
@@ -2165,13 +2215,35 @@ static void launch(const void *kernel, unsigned grid, unsigned block, size_t lds
 // the most rounds a pass-B unit of a stream-layout launch walked since the last reset (host
 // arithmetic of the planned units, every device; vh_stat_read("tile_stream_rounds"))
 static std::atomic<uint64_t> g_tile_stream_rounds{0};
+// host-image mirror (vh_stat_read): bins that left an image current; the most units on one ticket
+static std::atomic<uint64_t> g_host_image_bins{0}, g_host_image_tile_units{0};
+
+// what a bin hands the engine beside its plan: the host images on offer (Workspace::images),
+// and, for an odd row count, the launch that adds the last row (try_tiled).  A mirrored bin
+// runs it ahead of pass B -- after it the images are final -- once the plan can no longer be
+// refused; any other bin leaves it to the caller, after the passes as before
+struct TileBin {
+    std::vector<HostImageReq> *images = nullptr;
+    std::function<void()> last_row;
+    bool last_row_done = false;
+};
 
 static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64,
-                           const uint8_t *rowmask, const TileSwitches &sw) {
+                           const uint8_t *rowmask, const TileSwitches &sw, TileBin &bin) {
     TileScratch &ws = tile_scratch();
     std::lock_guard<std::mutex> ws_lock(ws.mu);
     TilePlan tpl;
     if (!plan_tiles(plan, fa_in, n, cells, nd_f64, rowmask != nullptr, sw, tpl)) return false;
+    // aggregators mirrored into their host image: cells final at pass B's flush, 8 bytes each
+    HostImageReq *req[MAX_FUSED_AGGS] = {};
+    bool mirror = false;
+    if (sw.host_image && !sw.debug && bin.images)
+        for (int k = 0; k < fa_in.na; k++) {
+            const int kind = fa_in.a[k].kind;
+            if (kind != VH_AGG_COUNT && kind != VH_AGG_SUM && kind != VH_AGG_SUM_MOMENT) continue;
+            for (HostImageReq &r : *bin.images)
+                if (r.grid == fa_in.a[k].grid) req[k] = &r, tpl.tp.image[k] = r.image_dev, mirror = true;
+        }
     const void *kernel_a = pass_a_kernel(tpl.a), *kernel_b = pass_b_kernel(tpl.b);
     if (!kernel_a || !kernel_b) fail(VH_ERR_RUNTIME, "tiled binning: the plan names a kernel that is not built");
     const TileLaunch L = plan_launch(tpl, n, cu_count(), blocks_per_cu(kernel_a, tpl.lds_a), sw);
@@ -2187,7 +2259,7 @@ static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t
     TileParams &tp = tpl.tp;  // the planner's part; the launch's and the scratch pointers follow
     tp.rowmask = rowmask, tp.debug = sw.debug;
     tp.W = W, tp.rows_per_wg = L.rows_per_wg;
-    ws.meta.ensure(L.meta.bytes);
+    ws.meta.ensure(L.meta.alloc);
     unsigned char *mb = ws.meta.as<unsigned char>();
     auto u32 = [&](uint64_t off) { return reinterpret_cast<uint32_t *>(mb + off); };
     auto u64 = [&](uint64_t off) { return reinterpret_cast<uint64_t *>(mb + off); };
@@ -2199,6 +2271,10 @@ static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t
 
     // ---- sample
     VH_HIP(hipMemsetAsync(d_hist, 0, 16 * (uint64_t)T, st));
+    if (mirror) {
+        tp.tickets = u32(L.meta.tickets), tp.tile_units = u32(L.meta.tunits);
+        VH_HIP(hipMemsetAsync(tp.tickets, 0, 4 * (uint64_t)T, st));
+    }
     {
         TimedScope ts("tile_sample");
         BinPlan p = plan;
@@ -2240,7 +2316,7 @@ static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t
     thread_local hipEvent_t sample_ev = nullptr;
     if (!sample_ev) VH_HIP(hipEventCreateWithFlags(&sample_ev, hipEventDisableTiming));
     const uint64_t dl_bytes = (16 * (uint64_t)T + 8 * L.sblocks + 255) & ~uint64_t(255);
-    tstage.ensure(dl_bytes + 24 * (uint64_t)T + sizeof(WorkUnit) * L.max_units + 1024);
+    tstage.ensure(dl_bytes + 28 * (uint64_t)T + sizeof(WorkUnit) * L.max_units + 1024);
     VH_HIP(hipMemcpyAsync(tstage.ptr, d_hist, 16 * (uint64_t)T, hipMemcpyDeviceToHost, st));
     VH_HIP(hipMemcpyAsync(tstage.as<char>() + 16 * (uint64_t)T, d_brange, 8 * L.sblocks, hipMemcpyDeviceToHost, st));
     VH_HIP(hipEventRecord(sample_ev, st));
@@ -2258,13 +2334,19 @@ static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t
     if (!size_regions(tpl, L, n, hist, brange, reg)) return false;
     std::vector<WorkUnit> units;
     plan_units(tpl, L, n, cu_count(), hist, reg.sampled, units);
+    std::vector<uint32_t> tile_units;  // mirrored launches: units per tile, the coldest tiles' units first
+    uint64_t most_units = 0;
+    if (mirror) {
+        most_units = count_tile_units(units, T, tile_units);
+        mirror_order_units(n, cu_count(), hist, reg.sampled, tile_units, units);
+    }
     if (L.stream_layout) {  // vh_stat_read("tile_stream_rounds"): the most rounds a unit walks
         const uint64_t r = max_unit_rounds(L, units);
         uint64_t seen = g_tile_stream_rounds.load(std::memory_order_relaxed);
         while (seen < r && !g_tile_stream_rounds.compare_exchange_weak(seen, r, std::memory_order_relaxed)) {}
     }
     if (!L.stream_layout) setup(reg.stride, reg.stotal);
-    char *upl = tstage.as<char>() + dl_bytes;  // upload region: cap | toff | sstart | scap | units
+    char *upl = tstage.as<char>() + dl_bytes;  // upload region: cap | toff | sstart | scap | units | tile_units
     auto upload = [&](uint64_t meta_off, const void *src, uint64_t bytes) {
         memcpy(upl, src, bytes);
         VH_HIP(hipMemcpyAsync(mb + meta_off, upl, bytes, hipMemcpyHostToDevice, st));
@@ -2275,8 +2357,17 @@ static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t
     upload(L.meta.sstart, reg.sstart.data(), 8 * (uint64_t)T);
     upload(L.meta.scap, reg.scap.data(), 4 * (uint64_t)T);
     if (!units.empty()) upload(L.meta.units, units.data(), sizeof(WorkUnit) * units.size());
+    if (mirror) {
+        upload(L.meta.tunits, tile_units.data(), 4 * (uint64_t)T);
+        uint64_t seen = g_host_image_tile_units.load(std::memory_order_relaxed);
+        while (seen < most_units && !g_host_image_tile_units.compare_exchange_weak(seen, most_units, std::memory_order_relaxed)) {}
+    }
     // ---- pass A (launched before the sample came back in the stream layout)
     if (!L.stream_layout) launch_pass_a();
+    if (mirror && bin.last_row) {  // nothing may write the grids once pass B has mirrored them
+        bin.last_row();
+        bin.last_row_done = true;
+    }
     // ---- pass B
     TimedScope ts("tile_reduce");
     // min / max: native-atomic scratch in the LDS cell form, merged after pass B (past 1 GiB
@@ -2299,6 +2390,17 @@ static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t
     }
     void *args_b[] = {&fa, &tp, &d_units};
     launch(kernel_b, (unsigned)units.size(), TB_THREADS, tpl.lds_b, args_b);
+    if (mirror) {
+        // tiles without a unit (none with today's plan_units: every tile gets g_min >= 1) are
+        // copied here, so that the images are written in full either way
+        for (const CellRange &r : mirror_uncovered(tp, tile_units))
+            for (int k = 0; k < fa.na; k++)
+                if (req[k])
+                    copy_to_host(static_cast<char *>(req[k]->image) + 8 * r.first, static_cast<const char *>(fa.a[k].grid) + 8 * r.first,
+                                 8 * r.n, st);
+        for (int k = 0; k < fa.na; k++)
+            if (req[k]) req[k]->written = true;
+    }
     for (int k = 0; k < fa.na; k++) {
         if (!tp.mmtmp[k]) continue;
         hipLaunchKernelGGL(k_mm_merge, dim3(blocks_for(cells, 256, 8)), dim3(256), 0, st, fa.a[k].grid, tp.mmtmp[k], cells,
@@ -2313,7 +2415,7 @@ static bool try_tiled_core(const BinPlan &plan, const FusedAggs &fa_in, uint64_t
 // the plan runs as unmasked -- counts of every kept row, no flag entries.  Only when a fast
 // kernel takes the plan; otherwise the masks go to the generic pass A as before.  (C2 with a
 // selection: generic pass A 12.0 ms, profiles/r06_mask.txt.)  VH_TILE_ROWMASK=0: off.
-static bool try_tiled_impl(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64) {
+static bool try_tiled_impl(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64, TileBin &bin) {
     const uint8_t *m = fa_in.na > 0 ? fa_in.a[0].mask : nullptr;
     for (int k = 1; k < fa_in.na && m; k++)
         if (fa_in.a[k].mask != m) m = nullptr;
@@ -2323,17 +2425,19 @@ static bool try_tiled_impl(const BinPlan &plan, const FusedAggs &fa_in, uint64_t
     if (m && sw.rowmask) {
         FusedAggs f2 = fa_in;
         for (int k = 0; k < f2.na; k++) f2.a[k].mask = nullptr;
-        if (try_tiled_core(plan, f2, n, cells, nd_f64, m, sw)) return true;
+        if (try_tiled_core(plan, f2, n, cells, nd_f64, m, sw, bin)) return true;
     }
-    return try_tiled_core(plan, fa_in, n, cells, nd_f64, nullptr, sw);
+    return try_tiled_core(plan, fa_in, n, cells, nd_f64, nullptr, sw, bin);
 }
 
 bool try_tiled(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t cells, int nd_f64, Workspace &ws) {
     if (n < (1u << 20) || cells >= (1ull << 40)) return false;
+    TileBin bin;
+    bin.images = &ws.images;
     if ((n & 1) && !fa_in.generic_vals && (nd_f64 > 0 || ord_fast_ok(plan, fa_in))) {
         // the fast pass A reads row pairs: tile all rows but the last, which takes the
-        // global-atomic path
-        if (!try_tiled_impl(plan, fa_in, n - 1, cells, nd_f64)) return false;
+        // global-atomic path (after the passes; ahead of pass B when it mirrors host images: one
+        // add commutes with the units' adds, whose order is not fixed either)
         BinPlan p1 = plan;
         FusedAggs f1 = fa_in;
         for (int d = 0; d < p1.nb; d++) {
@@ -2344,10 +2448,12 @@ bool try_tiled(const BinPlan &plan, const FusedAggs &fa_in, uint64_t n, uint64_t
             if (f1.a[k].data) f1.a[k].data += n - 1;
             if (f1.a[k].mask) f1.a[k].mask += n - 1;
         }
-        launch_fused(p1, f1, 1, cells, nd_f64, ws);
+        bin.last_row = [&]() { launch_fused(p1, f1, 1, cells, nd_f64, ws); };
+        if (!try_tiled_impl(plan, fa_in, n - 1, cells, nd_f64, bin)) return false;
+        if (!bin.last_row_done) bin.last_row();
         return true;
     }
-    return try_tiled_impl(plan, fa_in, n, cells, nd_f64);
+    return try_tiled_impl(plan, fa_in, n, cells, nd_f64, bin);
 }
 
 uint64_t stat_tile_overflow(bool reset) {
@@ -2363,6 +2469,12 @@ uint64_t stat_tile_overflow(bool reset) {
 
 uint64_t stat_tile_stream_rounds(bool reset) {
     return reset ? g_tile_stream_rounds.exchange(0) : g_tile_stream_rounds.load();
+}
+
+void note_host_image_bin() { g_host_image_bins.fetch_add(1, std::memory_order_relaxed); }
+uint64_t stat_host_image_bins(bool reset) { return reset ? g_host_image_bins.exchange(0) : g_host_image_bins.load(); }
+uint64_t stat_host_image_tile_units(bool reset) {
+    return reset ? g_host_image_tile_units.exchange(0) : g_host_image_tile_units.load();
 }
 
 }  // namespace vh

@@ -204,8 +204,14 @@ class Grid:
 
     def bin(self, aggs, length=None):
         aggs = list(aggs)
+        # device-resident binner columns: the aggregators may register their host images, which
+        # the tiled engine then fills from inside the bin (host columns are streamed in many
+        # bins per query, each of which would write the image: not registered)
+        device = all(isinstance(getattr(b, "_data_ref", None), DeviceArray) and
+                     isinstance(getattr(b, "_mask_ref", None), (DeviceArray, type(None))) for b in self._binners)
         for a in aggs:
             a._before_device_use()
+            a._offer_host_image(device)
         arr = (ctypes.c_void_p * max(1, len(aggs)))(*[a._handle for a in aggs])
         has_length = length is not None
         _lib.call("vh_grid_bin", self._handle, arr, len(aggs), int(length) if has_length else 0, int(has_length))
@@ -245,6 +251,9 @@ class Aggregator:
         self._exposed = False    # a view was handed out: the host image may be written by the user
         self._device_newer = True
         self._refs = {}
+        self._image_ptr = None    # address of the host image registered with the library
+        self._mirror_host = True  # False: never register one (the result stays in HBM, or the
+        #                           grid's address was handed out: writers the library cannot see)
 
     # ---- data ----------------------------------------------------------------
     def set_data(self, ar, index=0):
@@ -275,10 +284,39 @@ class Aggregator:
     def _release_host(self):
         """The current host image now belongs to a result array (which keeps this object,
         and so the image, alive through its base): later reads get a fresh image."""
+        self._drop_host_image()  # before the image changes hands: no later bin may write it
         self._released = self._host
         self._host = None
         self._exposed = False
         self._device_newer = True
+
+    # grids whose cells are final when the tiled engine's last kernel flushes them, of at least
+    # the size from which the library reads back through mapped memory (vh_agg_set_host_image)
+    _IMAGE_KINDS = ("AggCount", "AggSum", "AggSumMoment")
+    _IMAGE_MIN_BYTES = 256 << 10
+
+    def _offer_host_image(self, device_binners):
+        """Before a bin: register the page-locked host image (allocating it if need be) so the
+        library can fill it from inside the bin and the read-back becomes a wait, when the
+        grid is one the library mirrors and every column is device-resident; otherwise make
+        sure none is registered."""
+        ok = (device_binners and self._mirror_host and self._kind in self._IMAGE_KINDS
+              and self._grid_dtype.itemsize == 8 and self._nbytes >= self._IMAGE_MIN_BYTES
+              and all(isinstance(r, DeviceArray) for r in self._refs.values()))
+        if not ok:
+            self._drop_host_image()
+            return
+        if self._host is None:
+            self._host = _lib.pinned_empty(self._grid.length1d, self._grid_dtype)
+            self._device_newer = True
+        if self._image_ptr != self._host.ctypes.data:
+            _lib.call("vh_agg_set_host_image", self._handle, self._host.ctypes.data, self._nbytes)
+            self._image_ptr = self._host.ctypes.data
+
+    def _drop_host_image(self):
+        if self._image_ptr is not None:
+            _lib.call("vh_agg_set_host_image", self._handle, None, 0)
+            self._image_ptr = None
 
     def _ensure_host(self):
         if self._host is None:
@@ -316,6 +354,7 @@ class Aggregator:
         """HBM address of the grid (length1d items of the grid dtype)."""
         p, p2 = ctypes.c_void_p(), ctypes.c_void_p()
         _lib.call("vh_agg_device_ptr", self._handle, ctypes.byref(p), ctypes.byref(p2))
+        self._image_ptr, self._mirror_host = None, False  # the library dropped the registration
         return p.value
 
     def occupancy(self, begin=0, end=None):
@@ -358,6 +397,7 @@ class Aggregator:
         """HBM address of AggFirst's order grid."""
         p, p2 = ctypes.c_void_p(), ctypes.c_void_p()
         _lib.call("vh_agg_device_ptr", self._handle, ctypes.byref(p), ctypes.byref(p2))
+        self._image_ptr, self._mirror_host = None, False  # the library dropped the registration
         return p2.value
 
     def order_grid(self):

@@ -109,6 +109,8 @@ class TaskPartAggregation:
             aggs = []
             for _ in selections:
                 agg = desc._create_operation(self.grid)
+                if getattr(desc, "keep_device", False) and not selection_waslist:
+                    agg._mirror_host = False  # finished on the device: no host image to fill
                 self.nbytes += agg.__sizeof__()
                 aggs.append(agg)
             self.aggregations.append((desc, selections, aggs, selection_waslist))
