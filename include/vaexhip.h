@@ -457,10 +457,23 @@ int vh_combine_keys(uint64_t n, int nkeys, const void *const *cols, const int *d
  * map_ordinal, hash_primitives.hpp:468-516,543-583) with sorted ordinals. */
 int vh_dense_rank_i64(uint64_t n, const int64_t *keys, int32_t *rank, int64_t *distinct, uint64_t *m);
 
-/* stable ascending argsort of an HBM key column of `dtype` (order: int64, HBM): the Grouper
- * sort=True order (groupby.py:137-156 sorts the set's keys; NaN after every number, -0.0 ==
- * 0.0 keep their order); n < 2^32 */
-int vh_argsort(uint64_t n, const void *keys, int dtype, int64_t *order);
+/* ---- row order on HBM columns (sort.hip) ---------------------------------------
+ * The kept rows of a byte mask (the reference's mask.first(k)): the positions i < n with
+ * mask[i] != 0, ascending, into rows_out (signed, out_itemsize 4 or 8 bytes each; 4 only while
+ * n < 2^31), which has room for n items; *m are written.  Every buffer is in HBM. */
+int vh_mask_rows(const uint8_t *mask, uint64_t n, int out_itemsize, void *rows_out, uint64_t *m);
+/* Stable argsort of 1 to 16 HBM key columns of n rows (keys[k] of dtypes[k], the first key the
+ * most significant): DataFrame.sort (dataframe.py:4420-4461) and the Grouper sort=True order
+ * (groupby.py:137-156).  rows == NULL: every row (m must equal n); else rows is an ascending
+ * list of m row numbers (what vh_mask_rows writes) and only those rows are sorted.  perm_out
+ * takes m row numbers of the columns, so one vh_take finishes a sort; rows and perm_out hold
+ * signed items of rows_itemsize bytes (4 only while n < 2^31) in HBM.
+ * The order is np.lexsort(keys[::-1]) over those rows (one key: np.argsort(kind="stable")):
+ * stable, NaN after every number and all NaN equal, -0.0 == 0.0.  descending != 0: the exact
+ * reverse of that order (tied rows in reverse row order).
+ * VH_ERR_ARG: a row number in rows outside [0, n) (nothing is written then). */
+int vh_argsort(int nkeys, const void *const *keys, const int *dtypes, uint64_t n, const void *rows, int rows_itemsize,
+               uint64_t m, int descending, void *perm_out);
 
 /* group labels of combined keys (the inverse of vh_combine_keys; groupby.py:248-288 decodes
  * the GrouperCombined bins back to per-key labels): v = table ? table[ck[i]] : ck[i],

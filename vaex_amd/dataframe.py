@@ -384,10 +384,13 @@ class DataFrame:
         i2 = self._length if i2 is None else i2
         fm = self.evaluate_filter_mask(i1, i2) if (filtered and self.filtered) else None
         if isinstance(fm, DeviceArray):
-            # the filtered rows of an HBM frame, read back (the compaction happens on the host)
+            # the filtered rows of an HBM frame: an HBM value is compacted on the device
+            # (mask_rows + vh_take) and only the kept rows are read back
             v = self._eval_host(expression, i1, i2)
-            v = v.to_numpy() if isinstance(v, DeviceArray) else np.asarray(v)
-            return v[fm.to_numpy().astype(bool)]
+            if isinstance(v, DeviceArray):
+                from .sort import compact_device
+                return compact_device(v, fm).to_numpy()
+            return np.asarray(v)[fm.to_numpy().astype(bool)]
         return self._eval_host(expression, i1, i2, fm)
 
     def evaluate_filter_mask(self, i1, i2):
@@ -1226,11 +1229,32 @@ class DataFrame:
     def take(self, indices, filtered=True, dropfilter=True):
         """A new frame of the rows ``indices`` (a host array or a DeviceArray of int32 / int64):
         HBM columns are gathered on the device (``vh_take``), host columns on the host threads;
-        virtual columns, variables and categories carry over.  On a filtered frame only
-        ``filtered=False, dropfilter=False`` is supported: the indices are unfiltered row
-        numbers and the filter stays on the result (the other forms raise NotImplementedError)."""
+        virtual columns, variables, categories and selections carry over.  On a filtered frame
+        only ``filtered=False, dropfilter=False`` is supported: the indices are unfiltered row
+        numbers and the filter stays on the result (the other forms raise NotImplementedError);
+        ``df.extract().take(indices)`` takes from the kept rows."""
         from .join import take
         return take(self, indices, filtered=filtered, dropfilter=dropfilter)
+
+    def extract(self):
+        """dataframe.py:4216-4233: a frame of the rows the filter keeps, with the filter dropped
+        (a copy for an unfiltered frame).  HBM columns are compacted in HBM (``mask_rows`` of the
+        filter's device mask, then ``vh_take``); a host frame uses boolean indexing."""
+        from .sort import extract
+        return extract(self)
+
+    def sort(self, by, ascending=True, kind="quicksort"):
+        """dataframe.py:4420-4461: the rows in the order of ``by``, an expression or a list /
+        tuple of expressions (the first the most significant).  The order is
+        ``np.argsort(kind="stable")`` / ``np.lexsort``: stable (``kind`` is accepted, and stable
+        is a valid answer for every NumPy kind), NaN last, ``-0.0 == 0.0``; ``ascending=False``
+        is the exact reverse.  datetime keys sort as int64.  The result goes through ``take``:
+        virtual columns, variables, categories and selections carry over, and on a filtered
+        frame it holds only the kept rows, with the filter dropped.  On a frame with HBM columns
+        the keys are argsorted on the device (``vh_argsort`` over the kept rows) and HBM columns
+        are gathered in HBM; a frame with no HBM column is ordered by NumPy."""
+        from .sort import sort
+        return sort(self, by, ascending=ascending, kind=kind)
 
     def join(self, other, on=None, left_on=None, right_on=None, lprefix="", rprefix="", lsuffix="", rsuffix="",
              how="left", allow_duplication=False, prime_growth=False, cardinality_other=None, inplace=False):
@@ -1294,18 +1318,6 @@ class DataFrame:
         for k, v in self.columns.items():
             out[k] = v.to_numpy() if isinstance(v, DeviceArray) else np.asarray(v)
         return out
-
-    def sort(self, by, ascending=True):
-        key = self.evaluate(by)
-        key = key.to_numpy() if isinstance(key, DeviceArray) else np.asarray(key)
-        order = np.argsort(key, kind="stable")
-        if not ascending:
-            order = order[::-1]
-        cols = {}
-        for k, v in self.columns.items():
-            v = v.to_numpy() if isinstance(v, DeviceArray) else v
-            cols[k] = v[order]
-        return DataFrame(cols, executor=self.executor)
 
     def __repr__(self):
         return f"DataFrame({self._length} rows, columns={self.get_column_names()})"

@@ -70,15 +70,12 @@ class Grouper(BinnerBase):
 
 def _device_argsort(values):
     """Stable ascending order of a key array (NaN last), computed on the GPU (vh_argsort)."""
-    from . import _lib
     from .device import DeviceArray
+    from .superutils import argsort_device
     values = np.ascontiguousarray(values)
     if not len(values):
         return np.empty(0, np.int64)
-    keys = DeviceArray.from_numpy(values)
-    out = DeviceArray(len(values), np.int64)
-    _lib.call("vh_argsort", len(values), keys.ptr, _lib.dtype_code(values.dtype)[0], out.ptr)
-    return out.to_numpy()
+    return argsort_device([DeviceArray.from_numpy(values)]).to_numpy().astype(np.int64)
 
 
 # integer keys whose value range is at most this many cells are binned densely

@@ -129,17 +129,26 @@ def _like(df, columns):
     return new
 
 
+def take_rows(df, indices, dropfilter=False):
+    """A new frame of the unfiltered rows ``indices`` (host array or DeviceArray of int32 /
+    int64) with the virtual columns, variables, categories and selections of ``df``; its filter
+    stays on the result unless ``dropfilter`` (``sort`` / ``extract`` drop it: sort.py)."""
+    cols = gather(df.columns, indices, df.length_unfiltered())
+    new = _like(df, cols)
+    new._length = len(indices)
+    if dropfilter:
+        new._filter = None
+    return new
+
+
 def take(df, indices, filtered=True, dropfilter=True):
     """dataframe.py take: a new frame of the rows ``indices`` (host array or DeviceArray of
     int32 / int64; unfiltered row numbers).  On a filtered frame only ``filtered=False,
     dropfilter=False`` is supported (what the join needs): the indices address unfiltered rows
-    and the filter stays on the result."""
+    and the filter stays on the result.  ``df.extract().take(indices)`` takes from the kept rows."""
     if df.filtered and (filtered or dropfilter):
         raise NotImplementedError("take on a filtered frame: only filtered=False, dropfilter=False")
-    cols = gather(df.columns, indices, df.length_unfiltered())
-    new = _like(df, cols)
-    new._length = len(indices)
-    return new
+    return take_rows(df, indices)
 
 
 def _concat(a, b):
@@ -268,7 +277,7 @@ def join(df, other, on=None, left_on=None, right_on=None, lprefix="", rprefix=""
             if not len(lookup_left):
                 continue
             n_now = left.length_unfiltered()
-            more = take(left, lookup_left, filtered=False, dropfilter=False)
+            more = take_rows(left, lookup_left)
             left = _like(left, {k: _concat(c, more.columns[k]) for k, c in left.columns.items()})
             left._length = n_now + len(lookup_left)
             lookup = _concat(lookup, lookup_right if on_device else lookup_right.astype(lookup_dtype))
@@ -279,7 +288,7 @@ def join(df, other, on=None, left_on=None, right_on=None, lprefix="", rprefix=""
                 matched = lookup != -1
                 rows, lookup = np.where(matched)[0], lookup[matched]
             # the indices can still refer to filtered rows, so the filter is not dropped
-            left = take(left, rows, filtered=False, dropfilter=False)
+            left = take_rows(left, rows)
             masked = False
 
     # renaming, so that all column names are unique (join.py:229-253)

@@ -9,7 +9,9 @@ bindings ``hash_primitives.cpp:26-73``): ``update``, ``key_array``, ``map_ordina
 of ``value_counts``, sits beside it over the library's hash counter, and ``index_hash_<dtype>``
 (``hash_primitives.hpp:623-900``), the key -> row map of ``DataFrame.join``, over the library's
 index, with the device gather (``take_device``) and the inner join's compaction
-(``index_matched``) a join needs next to it.
+(``index_matched``) a join needs next to it.  ``argsort_device`` and ``mask_rows`` are the two
+primitives of ``DataFrame.sort`` / ``extract`` (sort.py): the stable
+lexicographic order of device key columns and the kept rows of a device mask.
 
 Ordinals are assigned in first-appearance order over all ``update`` calls -- what a
 single-threaded reference ``update`` with ``nmaps = 1`` produces.  (With threads the
@@ -474,6 +476,58 @@ def index_matched(lookup):
     m = ctypes.c_uint64(0)
     _lib.call("vh_index_matched", lookup.ptr, lookup.dtype.itemsize, n, ctypes.byref(m), rows.ptr, out.ptr)
     return rows[:m.value], out[:m.value]
+
+
+# output positions a workgroup of the argsort's encode kernel takes per step (sort.hip: 256
+# lanes of SE_RPT = 4) and the most key columns one argsort takes (sort_plan.hpp SORT_MAX_KEYS)
+SORT_ENCODE_TILE = 1024
+SORT_MAX_KEYS = 16
+
+
+def _row_dtype(n):
+    """Row numbers of a column of n rows: int32 while they fit (they feed ``take_device``)."""
+    return np.dtype(np.int32 if n < 2 ** 31 else np.int64)
+
+
+def mask_rows(mask):
+    """The kept rows of a device byte mask (``vh_mask_rows``): ``np.flatnonzero(mask)`` as a
+    DeviceArray of int32 (int64 from 2^31 rows)."""
+    mask = _device_mask(mask)
+    n = len(mask)
+    rows = DeviceArray(n, _row_dtype(n))
+    m = ctypes.c_uint64(0)
+    _lib.call("vh_mask_rows", mask.ptr, n, rows.dtype.itemsize, rows.ptr, ctypes.byref(m))
+    return rows[:m.value]
+
+
+def argsort_device(keys, rows=None, ascending=True):
+    """Stable argsort of DeviceArray key columns on the device (``vh_argsort``): the row
+    numbers (DeviceArray of int32, int64 from 2^31 rows) in the order of
+    ``np.lexsort(keys[::-1])`` -- one key: ``np.argsort(kind="stable")`` -- so the first key is
+    the most significant, NaN sorts last and ``-0.0 == 0.0``; ``ascending=False`` gives the
+    exact reverse.  ``rows``: an ascending DeviceArray of row numbers (``mask_rows``); only
+    those rows are sorted.  datetime keys sort as int64."""
+    keys = [keys] if isinstance(keys, DeviceArray) else list(keys)
+    if not 1 <= len(keys) <= SORT_MAX_KEYS:
+        raise ValueError(f"argsort takes 1 to {SORT_MAX_KEYS} key columns")
+    for c in keys:
+        if not isinstance(c, DeviceArray):
+            raise TypeError("argsort_device takes DeviceArray key columns")
+    n = len(keys[0])
+    if any(len(c) != n for c in keys):
+        raise ValueError("key columns differ in length")
+    rdt = _row_dtype(n)
+    if rows is not None:
+        if not isinstance(rows, DeviceArray) or np.dtype(rows.dtype) != rdt:
+            raise TypeError(f"rows must be a DeviceArray of {rdt} (what mask_rows returns)")
+    m = n if rows is None else len(rows)
+    out = DeviceArray(m, rdt)
+    k = len(keys)
+    kptr = (ctypes.c_void_p * k)(*[c.ptr for c in keys])
+    codes = (ctypes.c_int * k)(*[_lib.dtype_code(c.dtype)[0] for c in keys])
+    _lib.call("vh_argsort", k, kptr, codes, n, None if rows is None else rows.ptr, rdt.itemsize, m,
+              0 if ascending else 1, out.ptr)
+    return out
 
 
 # edges of a lasso a workgroup stages in LDS at a time (select.hip PP_CHUNK) and the rows a
