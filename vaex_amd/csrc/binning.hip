@@ -115,7 +115,8 @@ __global__ __launch_bounds__(256) void k_agg(AggDev a, const uint64_t *idx, uint
             if (a.moment == 0) p = 1.0;
             else if (a.moment == 1) p = (double)value;
             else if (a.moment == 2) p = (double)value * (double)value;
-            else p = pow((double)value, (double)a.moment);
+            else if constexpr (is_float_t<T>::value) p = pow((double)value, (double)a.moment);
+            else p = moment_pow_int((double)value, a.moment);
             atomic_add_grid<G>(reinterpret_cast<G *>(a.grid) + c, (G)p);
         }
     }
@@ -167,7 +168,8 @@ __global__ __launch_bounds__(256) void k_agg_lds(BinPlan p, AggDev a, uint64_t n
             if (a.moment == 0) pw = 1.0;
             else if (a.moment == 1) pw = (double)value;
             else if (a.moment == 2) pw = (double)value * (double)value;
-            else pw = pow((double)value, (double)a.moment);
+            else if constexpr (is_float_t<T>::value) pw = pow((double)value, (double)a.moment);
+            else pw = moment_pow_int((double)value, a.moment);
             atomic_add_grid<G>(g + c, (G)pw);
         }
     }
@@ -294,7 +296,8 @@ __global__ __launch_bounds__(256) void k_agg_lds_c(AggDev a, const uint16_t *cel
                 if (a.moment == 0) pw = 1.0;
                 else if (a.moment == 1) pw = (double)value;
                 else if (a.moment == 2) pw = (double)value * (double)value;
-                else pw = pow((double)value, (double)a.moment);
+                else if constexpr (is_float_t<T>::value) pw = pow((double)value, (double)a.moment);
+                else pw = moment_pow_int((double)value, a.moment);
                 atomic_add_grid<G>(g + c, (G)pw);
             }
         }
