@@ -13,12 +13,14 @@ reference's plugin surface for that path:
 * :mod:`vaex_amd.hdf5`       -- memory-mapped vaex HDF5 files (read + export), no h5py
 * :mod:`vaex_amd.expr`       -- expressions / selections / filters evaluated on the GPU
 * :mod:`vaex_amd.selections` -- ``vaex.selections`` (modes, history nodes, the lasso)
+* :mod:`vaex_amd.datetime`   -- ``dt_*`` / ``td_*`` functions and the ``.dt`` / ``.td`` accessors
 """
 from . import _lib  # noqa: F401  (fails loudly if the HIP library is missing)
 from . import agg, superagg, superutils  # noqa: F401
 from .dataframe import DataFrame, Expression, RowLimitException, from_arrays, from_dict  # noqa: F401
 from .device import DeviceArray  # noqa: F401
 from .execution import ExecutorLocal, default_executor  # noqa: F401
+from .groupby import BinnerTime  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -11,6 +11,7 @@
 // evaluates EX_RPT rows per instruction fetch; the program is uniform, so every branch on
 // the opcode is a scalar branch.
 #include "common.hpp"
+#include "datetime_dev.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -45,6 +46,11 @@ enum : uint32_t {
     OP_WHERE = 110,
     OP_FLOORDIV_U = 120, OP_MOD_U = 121, OP_MIN_U = 122, OP_MAX_U = 123, OP_SHR_U = 124, OP_POW_U = 125,
 };
+
+// datetime64 / timedelta64 ticks as int64 slots (datetime_dev.hpp; vaex_amd/expr.py DT_OP):
+// unary, not is_math.  DT_FIELD: arg = field | unit << 4, an int32 / bool result; DT_CAST:
+// arg = from-unit | to-unit << 4 | timedelta bit << 8; TD_FIELD: arg = field | unit << 4
+enum : uint32_t { OP_DT_FIELD = 104, OP_DT_CAST = 105, OP_TD_FIELD = 106 };
 
 struct ExprProg {
     uint32_t code[EX_MAX_CODE];  // op | arg << 8
@@ -194,6 +200,17 @@ template <bool MATH> __device__ inline uint64_t unary(uint32_t op, uint32_t arg,
     return x;
 }
 
+// the datetime opcodes, apart from `unary`: k_expr_terms inlines `unary` for its conversions
+// and would pay registers (and waves of occupancy) for calendar code it never runs
+__device__ inline uint64_t unary_dt(uint32_t op, uint32_t arg, uint64_t x) {
+    const int64_t v = as_i(x);
+    switch (op) {
+    case OP_DT_FIELD: return (uint64_t)(int64_t)dt::dt_field_rt(arg & 15, (arg >> 4) & 15, v);
+    case OP_DT_CAST: return (uint64_t)dt::dt_cast_rt(arg & 15, (arg >> 4) & 15, v);
+    default: return dt::td_field_rt(arg & 15, (arg >> 4) & 15, v);
+    }
+}
+
 // the comparisons on their own: all that k_expr_terms needs of `binary`, whose division and
 // float32 divmod bodies would otherwise cost that kernel registers (and a wave of occupancy)
 __device__ inline uint64_t compare(uint32_t op, uint64_t a, uint64_t b) {
@@ -324,6 +341,9 @@ __global__ __launch_bounds__(EX_THREADS) void k_expr(ExprProg prog, uint64_t n, 
 #pragma unroll
                     for (int d = 1; d < EX_DEPTH - 1; d++) s[r][d] = s[r][d + 1];
                 }
+            } else if (op >= OP_DT_FIELD && op <= OP_TD_FIELD) {
+#pragma unroll
+                for (int r = 0; r < EX_RPT; r++) s[r][0] = unary_dt(op, arg, s[r][0]);
             } else {
 #pragma unroll
                 for (int r = 0; r < EX_RPT; r++) s[r][0] = unary<MATH>(op, arg, s[r][0]);
@@ -433,6 +453,73 @@ __global__ __launch_bounds__(EX_THREADS) void k_expr_terms(ExprTerms t, uint64_t
     }
 }
 
+// ---- dt_<field>(column): the groupby-key shape COL DT_FIELD -------------------------------
+// groupby(t.dt.hour) and the like evaluate one datetime field of one int64 column into an int32
+// key column (a bool one for is_leap_year).  As in k_expr_terms each lane takes 8 consecutive
+// rows: four 16-byte loads, the field function with unit and field fixed at compile time (the
+// field switch runs once per 8 rows, its loop bodies are branch-free), two 16-byte stores (one
+// 8-byte store for the bool).  A ragged tail or a misaligned block goes element by element.
+template <int U, int F> __device__ inline void dt_field8(const uint64_t (&v)[EXT_RPT], int32_t (&o)[EXT_RPT]) {
+#pragma unroll
+    for (int r = 0; r < EXT_RPT; r++) o[r] = dt::dt_field<U, F>((int64_t)v[r]);
+}
+
+template <int U>
+__global__ __launch_bounds__(EX_THREADS) void k_expr_dtfield(const int64_t *col, int field, uint64_t n, void *out,
+                                                             int out_isz) {
+    const uint64_t stride = (uint64_t)gridDim.x * EX_THREADS * EXT_RPT;
+    for (uint64_t base = ((uint64_t)blockIdx.x * EX_THREADS + threadIdx.x) * EXT_RPT; base < n; base += stride) {
+        const uint32_t cnt = (uint32_t)min<uint64_t>(EXT_RPT, n - base);
+        uint64_t v[EXT_RPT];
+        load_slots8(col, VH_I64, base, cnt, v);
+        int32_t o[EXT_RPT];
+        switch (field) {
+        case dt::F_YEAR: dt_field8<U, dt::F_YEAR>(v, o); break;
+        case dt::F_MONTH: dt_field8<U, dt::F_MONTH>(v, o); break;
+        case dt::F_DAY: dt_field8<U, dt::F_DAY>(v, o); break;
+        case dt::F_DAYOFWEEK: dt_field8<U, dt::F_DAYOFWEEK>(v, o); break;
+        case dt::F_DAYOFYEAR: dt_field8<U, dt::F_DAYOFYEAR>(v, o); break;
+        case dt::F_QUARTER: dt_field8<U, dt::F_QUARTER>(v, o); break;
+        case dt::F_HALFYEAR: dt_field8<U, dt::F_HALFYEAR>(v, o); break;
+        case dt::F_HOUR: dt_field8<U, dt::F_HOUR>(v, o); break;
+        case dt::F_MINUTE: dt_field8<U, dt::F_MINUTE>(v, o); break;
+        case dt::F_SECOND: dt_field8<U, dt::F_SECOND>(v, o); break;
+        case dt::F_IS_LEAP_YEAR: dt_field8<U, dt::F_IS_LEAP_YEAR>(v, o); break;
+        default: dt_field8<U, dt::F_WEEKOFYEAR>(v, o); break;
+        }
+        if (out_isz == 4) {
+            int32_t *dst = static_cast<int32_t *>(out) + base;
+            if (cnt == EXT_RPT && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+                reinterpret_cast<int4 *>(dst)[0] = make_int4(o[0], o[1], o[2], o[3]);
+                reinterpret_cast<int4 *>(dst)[1] = make_int4(o[4], o[5], o[6], o[7]);
+            } else {
+                for (uint32_t r = 0; r < cnt; r++) dst[r] = o[r];
+            }
+        } else {
+            uint8_t *dst = static_cast<uint8_t *>(out) + base;
+            uint64_t word = 0;
+#pragma unroll
+            for (int r = 0; r < EXT_RPT; r++) word |= (uint64_t)(o[r] & 1) << (8 * r);
+            if (cnt == EXT_RPT && (reinterpret_cast<uintptr_t>(dst) & 7) == 0) {
+                *reinterpret_cast<uint64_t *>(dst) = word;
+            } else {
+                for (uint32_t r = 0; r < cnt; r++) dst[r] = (uint8_t)(word >> (8 * r));
+            }
+        }
+    }
+}
+
+// the program as COL DT_FIELD over an int64 column, with an int32 result (a 1-byte one for
+// is_leap_year); false: another shape
+static bool match_dtfield(const uint32_t *code, int ncode, const int *col_dtypes, int out_dtype, int &unit, int &field) {
+    if (ncode != 2 || (code[0] & 0xff) != OP_COL || (code[1] & 0xff) != OP_DT_FIELD) return false;
+    if (col_dtypes[code[0] >> 8] != VH_I64) return false;
+    field = (int)((code[1] >> 8) & 15);
+    unit = (int)((code[1] >> 12) & 15);
+    const int isz = dtype_itemsize(out_dtype);
+    return field == dt::F_IS_LEAP_YEAR ? isz == 1 : out_dtype == VH_I32;
+}
+
 // the program as T (T COMB)* [NOT_B] with T = COL [cvt] CONST [cvt] CMP, one COMB kind
 // (AND_I or OR_I) and a 1-byte output; false: another shape
 static bool match_terms(const uint32_t *code, int ncode, const uint64_t *consts, const void *const *cols,
@@ -511,6 +598,12 @@ extern "C" int vh_expr_eval(const uint32_t *code, int ncode, const uint64_t *con
             depth -= 2;
         } else if (is_binary(op)) {
             depth -= 1;
+        } else if (op == OP_DT_FIELD || op == OP_TD_FIELD) {
+            const int field = (int)(arg & 15), unit = (int)((arg >> 4) & 15);
+            if (unit > dt::U_D || field >= (op == OP_DT_FIELD ? (int)dt::N_FIELDS : (int)dt::N_TD_FIELDS))
+                fail(VH_ERR_ARG, "datetime field or unit out of range");
+        } else if (op == OP_DT_CAST) {
+            if ((int)(arg & 15) > dt::U_Y || (int)((arg >> 4) & 15) > dt::U_Y) fail(VH_ERR_ARG, "datetime cast unit out of range");
         }
         if (depth < 1) fail(VH_ERR_ARG, "malformed expression program (stack underflow)");
         maxd = std::max(maxd, depth);
@@ -534,6 +627,26 @@ extern "C" int vh_expr_eval(const uint32_t *code, int ncode, const uint64_t *con
         const uint64_t per_block = (uint64_t)EX_THREADS * EXT_RPT;
         const unsigned grid = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)cu_count() * 8);
         hipLaunchKernelGGL(k_expr_terms, dim3(grid), dim3(EX_THREADS), 0, stream(), terms, n, static_cast<uint8_t *>(out));
+        VH_HIP(hipGetLastError());
+    } else if (int unit = 0, field = 0; n && !getenv_off_expr("VH_EXPR_DTFIELD") &&
+                                       match_dtfield(code, ncode, col_dtypes, out_dtype, unit, field)) {
+        TimedScope ts("expr");
+        const uint64_t per_block = (uint64_t)EX_THREADS * EXT_RPT;
+        const unsigned grid = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)cu_count() * 8);
+        const int64_t *col = static_cast<const int64_t *>(cols[code[0] >> 8]);
+        const int isz = dtype_itemsize(out_dtype);
+#define VH_DTFIELD_LAUNCH(U) \
+    hipLaunchKernelGGL(k_expr_dtfield<U>, dim3(grid), dim3(EX_THREADS), 0, stream(), col, field, n, out, isz)
+        switch (unit) {
+        case dt::U_NS: VH_DTFIELD_LAUNCH(dt::U_NS); break;
+        case dt::U_US: VH_DTFIELD_LAUNCH(dt::U_US); break;
+        case dt::U_MS: VH_DTFIELD_LAUNCH(dt::U_MS); break;
+        case dt::U_S: VH_DTFIELD_LAUNCH(dt::U_S); break;
+        case dt::U_MIN: VH_DTFIELD_LAUNCH(dt::U_MIN); break;
+        case dt::U_H: VH_DTFIELD_LAUNCH(dt::U_H); break;
+        default: VH_DTFIELD_LAUNCH(dt::U_D); break;
+        }
+#undef VH_DTFIELD_LAUNCH
         VH_HIP(hipGetLastError());
     } else if (n) {
         TimedScope ts("expr");

@@ -160,6 +160,18 @@ class Expression:
         return self.df.data_type(self.expression)
 
     @property
+    def dt(self):
+        """expression.py ``DateTime`` accessor: ``df.t.dt.hour`` is ``dt_hour(t)`` (datetime.py)."""
+        from .datetime import DateTime
+        return DateTime(self)
+
+    @property
+    def td(self):
+        """expression.py ``TimeDelta`` accessor: ``df.d.td.days`` is ``td_days(d)``."""
+        from .datetime import TimeDelta
+        return TimeDelta(self)
+
+    @property
     def values(self):
         return self.df.evaluate(self.expression)
 
@@ -206,6 +218,19 @@ class Expression:
 def _ordinal_values(x, ordered_set):
     """functions.py:2441-2448 (host evaluation; the bin kernel fuses it instead)."""
     return ordered_set.map_ordinal(x)
+
+
+def _host_functions():
+    """The functions of the host expression namespace besides ``np``."""
+    from .datetime import FUNCTIONS
+    ns = {"_ordinal_values": _ordinal_values, "astype": _astype}
+    ns.update(FUNCTIONS)
+    return ns
+
+
+# whether a live datetime64 / timedelta64 column holds NaT: (column reference, answer), the
+# column held weakly like the mask cache's (an entry with a dead column goes)
+_nat_cache = []
 
 
 def _astype(x, data_type):
@@ -326,7 +351,7 @@ class DataFrame:
 
     # ---- evaluation --------------------------------------------------------------
     def _namespace(self, i1, i2, filter_mask=None):
-        ns = {"np": np, "_ordinal_values": _ordinal_values, "astype": _astype}
+        ns = {"np": np, **_host_functions()}
         for name, col in self.columns.items():
             ns[name] = col
         ns.update(self.variables)
@@ -349,7 +374,7 @@ class DataFrame:
             return self._eval_device(expression, i1, i2)
         if expression in self.virtual_columns:
             return self._eval_host(self.virtual_columns[expression], i1, i2, filter_mask)
-        ns = {"np": np, "_ordinal_values": _ordinal_values, "astype": _astype}
+        ns = {"np": np, **_host_functions()}
         ns.update(self.variables)
         for name, col in self.columns.items():
             if name in expression:
@@ -425,6 +450,26 @@ class DataFrame:
                 del cache[:]
             cache.append((key, [_column_ref(c) for c in cols], values, m))
         return m
+
+    def _column_has_nat(self, name):
+        """Whether the datetime64 / timedelta64 column ``name`` holds NaT, asked by the device
+        expression compiler (expr.py: such a column does not compute on the device).  An HBM
+        column answers from a device min / max pass over its int64 bits, once per live column
+        object.  Like the mask cache, the answer is not told of writes into a column: a host
+        array that gets a NaT written in place afterwards keeps its "no NaT" answer, and the
+        device path would then compute an unspecified number for that row.  Columns are treated
+        as immutable; replace the column (a new array object) to change its values."""
+        from .expr import column_has_nat
+        col = self.columns[name]
+        with _mask_cache_lock:
+            _nat_cache[:] = [e for e in _nat_cache if e[0]() is not None]
+            for ref, answer in _nat_cache:
+                if ref() is col:
+                    return answer
+        answer = column_has_nat(col)
+        with _mask_cache_lock:
+            _nat_cache.append((_column_ref(col), answer))
+        return answer
 
     def data_type(self, expression):
         expression = str(expression)
@@ -869,8 +914,21 @@ class DataFrame:
         expression = _ensure_strings(expression)
         waslist, [expressions] = listify(expression)
         sel = selection if selection not in (None, False) else None
-        tasks = [self.executor.schedule(TaskMinMax(self, str(e), sel)) for e in expressions]
         dtype0 = self.data_type(expressions[0])
+        if dtype0.kind in "mM":
+            # datetime64 / timedelta64 scalars of the column's unit, exact: the min / max
+            # aggregators keep int64 (the float64 pre-pass below rounds ns ticks of this century
+            # to 256 ns)
+            parts = [(self.min(e, selection=selection, delay=True), self.max(e, selection=selection, delay=True))
+                     for e in expressions]
+
+            @delayed
+            def finish_time(*values):
+                v = np.array([np.asarray(x)[()] for x in values]).reshape(len(expressions), 2)
+                return unlistify(waslist, v) if waslist else v[0]
+
+            return self._delay(delay, finish_time(*[p for pair in parts for p in pair]))
+        tasks = [self.executor.schedule(TaskMinMax(self, str(e), sel)) for e in expressions]
 
         @delayed
         def finish(*values):

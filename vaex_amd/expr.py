@@ -48,6 +48,8 @@ OP = dict(COL=0, CONST=1, I2F=2, F2I=3, ROUND_F32=4, WRAP=5, U2F=6, I2F32=7, U2F
           LOG2=100, EXP2=101, TRUNC=102, RINT=103,
           WHERE=110,
           FLOORDIV_U=120, MOD_U=121, MIN_U=122, MAX_U=123, SHR_U=124, POW_U=125)
+# datetime64 / timedelta64 opcodes (the second enum of csrc/expr.hip; unary, an immediate each)
+DT_OP = dict(DT_FIELD=104, DT_CAST=105, TD_FIELD=106)
 # the opcodes that pop two slots and push one (expr.hip is_binary)
 BINARY = frozenset(OP[k] for k in (
     "ADD_F SUB_F MUL_F DIV_F FLOORDIV_F MOD_F POW_F MIN_F MAX_F ARCTAN2 FLOORDIV_F32 MOD_F32 "
@@ -68,8 +70,52 @@ FUNCTIONS = {
 PREDICATES = {"isnan": (np.isnan, "ISNAN"), "isfinite": (np.isfinite, "ISFINITE"), "isinf": (np.isinf, "ISINF")}
 
 
+# datetime64 / timedelta64 (csrc/datetime_dev.hpp mirrors these numbers): the units, the dt_*
+# fields (int32, is_leap_year bool: pandas 2's dtypes) and the td_* fields
+DT_UNITS = ["ns", "us", "ms", "s", "m", "h", "D", "W", "M", "Y"]
+DT_FIELD_UNITS = DT_UNITS[:7]  # field functions take these; coarser columns are cast first
+DT_FIELDS = ["year", "month", "day", "dayofweek", "dayofyear", "quarter", "halfyear", "hour", "minute", "second",
+             "is_leap_year", "weekofyear"]
+TD_FIELDS = {"days": (0, np.int64), "seconds": (1, np.int32), "microseconds": (2, np.int32),
+             "nanoseconds": (3, np.int32), "total_seconds": (4, np.float64)}
+INT64_MIN = -(1 << 63)  # NaT
+
+
 class UnsupportedExpression(ValueError):
     pass
+
+
+def _unit(dt):
+    """the index of a datetime64 / timedelta64 dtype's unit in DT_UNITS"""
+    unit, count = np.datetime_data(dt)
+    if count != 1 or unit not in DT_UNITS:
+        raise UnsupportedExpression(f"dtype {dt}: units are {', '.join(DT_UNITS)}")
+    return DT_UNITS.index(unit)
+
+
+def column_has_nat(col):
+    """Whether a datetime64 / timedelta64 column holds NaT (INT64_MIN).  An HBM column answers
+    from the device min / max pass over its int64 bits; that pass reports float64, in which the
+    512 values from INT64_MIN up are one number, so a minimum that low is settled exactly by a
+    device `== INT64_MIN` mask and its maximum."""
+    from .device import DeviceArray
+    if not isinstance(col, DeviceArray):
+        return bool(np.isnat(np.asarray(col)).any())
+    n = len(col)
+    if n == 0:
+        return False
+    lo, hi = ctypes.c_double(), ctypes.c_double()
+    code = _lib.DTYPE_CODE["int64"]
+    _lib.call("vh_minmax", col.ptr, n, code, 0, None, _lib.LOC_DEVICE, ctypes.byref(lo), ctypes.byref(hi))
+    if lo.value > float(INT64_MIN):
+        return False
+    mask = DeviceArray.empty(n, np.uint8)
+    prog = (ctypes.c_uint32 * 3)(OP["COL"], OP["CONST"], OP["EQ_I"])
+    _lib.call("vh_expr_eval", prog, 3, (ctypes.c_uint64 * 1)(1 << 63), 1, (ctypes.c_void_p * 1)(col.ptr),
+              (ctypes.c_int * 1)(code), 1, n, _lib.DTYPE_CODE["uint8"], mask.ptr)
+    _lib.call("vh_minmax", mask.ptr, n, _lib.DTYPE_CODE["uint8"], 0, None, _lib.LOC_DEVICE, ctypes.byref(lo),
+              ctypes.byref(hi))
+    return hi.value > 0
 
 
 class _Typed:
@@ -102,13 +148,22 @@ class Compiler:
     def _const(self, value):
         if isinstance(value, bool):
             bits, dt = int(value), np.bool_
-        elif isinstance(value, (int, np.integer)):
+        elif isinstance(value, (int, np.integer)) and not isinstance(value, np.timedelta64):
             value = int(value)
             if not -(1 << 63) <= value < (1 << 64):
                 raise UnsupportedExpression("integer constant out of 64-bit range")
             bits, dt = value & 0xFFFFFFFFFFFFFFFF, np.int64
         elif isinstance(value, (float, np.floating)):
             bits, dt = int(np.array(float(value)).view(np.uint64)), np.float64
+        elif isinstance(value, (np.datetime64, np.timedelta64)):
+            if np.isnat(value):
+                raise UnsupportedExpression("a NaT constant")
+            _unit(value.dtype)
+            bits = int(value.astype(np.int64)) & 0xFFFFFFFFFFFFFFFF
+            if bits not in self.consts:
+                self.consts.append(bits)
+            # a numpy scalar with a unit: strong in promotion, converted on the host by _to_unit
+            return _Typed([OP["CONST"] | self.consts.index(bits) << 8], value.dtype, scalar=value)
         else:
             raise UnsupportedExpression(f"constant {value!r}")
         # the pool may hold constants that no instruction uses in the end (a weak scalar is
@@ -121,10 +176,16 @@ class Compiler:
     def _column(self, name):
         col = self.df.columns[name]
         dt = np.dtype(col.dtype)
-        if dt.kind not in "biuf" or not dt.isnative:
+        if dt.kind not in "biufmM" or not dt.isnative:
             raise UnsupportedExpression(f"column {name!r} of dtype {dt}")
         if np.ma.isMaskedArray(col):
             raise UnsupportedExpression(f"masked column {name!r}")
+        if dt.kind in "mM":
+            # a program has one result dtype and does plain int64 arithmetic: pandas answers NaT
+            # rows with NaN, numpy propagates NaT, so only NaT-free columns compute here
+            _unit(dt)
+            if self.df._column_has_nat(name):
+                raise UnsupportedExpression(f"column {name!r} holds NaT (not-a-time) values")
         if name not in self.columns:
             if len(self.columns) >= MAX_COLS:
                 raise UnsupportedExpression("too many columns")
@@ -193,6 +254,8 @@ class Compiler:
             return self.visit(ast.parse(self.df.virtual_columns[name], mode="eval"))
         if name in self.df.variables:
             v = self.df.variables[name]
+            if isinstance(v, (np.datetime64, np.timedelta64)):
+                return self._const(v)
             if isinstance(v, (bool, int, float, np.integer, np.floating, np.bool_)):
                 return self._const(v.item() if isinstance(v, np.generic) else v)
             raise UnsupportedExpression(f"variable {name!r} is not a scalar")
@@ -216,7 +279,11 @@ class Compiler:
         if a.scalar is not None and b.scalar is not None:
             with np.errstate(all="ignore"):
                 v = ufunc(a.scalar, b.scalar)
+            if isinstance(v, (np.datetime64, np.timedelta64)):
+                return self._const(v)
             return self._const(v.item() if isinstance(v, np.generic) else v)
+        if a.dtype.kind in "mM" or b.dtype.kind in "mM":
+            return self._arith_time(opname, a, b, dt)
         if dt.kind == "b":  # numpy: bool + bool = or, bool * bool = and
             if opname in ("+", "*"):
                 return _Typed(a.code + b.code + [OP["OR_I" if opname == "+" else "AND_I"]], dt)
@@ -252,6 +319,50 @@ class Compiler:
             code.append(OP[op])
         return _Typed(self._finish(code, dt), dt)
 
+    def _to_unit(self, t, dtype):
+        """code leaving the datetime64 / timedelta64 value t in the unit of ``dtype`` (of t's
+        kind): a constant is converted on the host, a column expression by DT_CAST."""
+        dtype = np.dtype(dtype)
+        if t.dtype == dtype:
+            return list(t.code)
+        if t.scalar is not None:
+            v = t.scalar.astype(dtype)
+            if v.astype(t.dtype) != t.scalar and _unit(dtype) < _unit(t.dtype):
+                raise UnsupportedExpression(f"constant {t.scalar!r} overflows {dtype}")
+            return list(self._const(v).code)
+        arg = _unit(t.dtype) | _unit(dtype) << 4 | (t.dtype.kind == "m") << 8
+        return list(t.code) + [DT_OP["DT_CAST"] | arg << 8]
+
+    def _arith_time(self, opname, a, b, dt):
+        """datetime64 / timedelta64 arithmetic as numpy types it (dt is numpy's result dtype):
+        M - M -> m, M +- m, m +- m, m * int, m // int, m // m -> int64, m / m -> float64.  Mixed
+        units meet in numpy's result unit: a DT_CAST on the coarser column operand."""
+        ka, kb = a.dtype.kind, b.dtype.kind
+        if opname in ("+", "-") and ka in "mM" and kb in "mM":
+            # the operands in the result's unit, each in its own kind
+            unit = np.datetime_data(dt)[0]
+            x = self._to_unit(a, f"{ka}8[{unit}]")
+            y = self._to_unit(b, f"{kb}8[{unit}]")
+            return _Typed(x + y + [OP["ADD_I" if opname == "+" else "SUB_I"]], dt)
+        int_a = ka in "iu" and (a.scalar is None or type(a.scalar) is int)
+        int_b = kb in "iu" and (b.scalar is None or type(b.scalar) is int)
+        if opname == "*" and dt.kind == "m" and ((ka == "m" and int_b) or (kb == "m" and int_a)):
+            return _Typed(a.code + b.code + [OP["MUL_I"]], dt)
+        if opname == "//" and ka == "m" and int_b and dt.kind == "m":
+            # numpy's timedelta64 // integer is C's truncating division (timedelta64 //
+            # timedelta64 floors): the floor plus one where the remainder is not zero and the
+            # signs differ
+            zero = self._const(0).code
+            return _Typed(a.code + b.code + [OP["FLOORDIV_I"]] + a.code + b.code + [OP["MOD_I"]] + zero + [OP["NE_I"]]
+                          + a.code + b.code + [OP["XOR_I"]] + zero + [OP["LT_I"], OP["AND_I"], OP["ADD_I"]], dt)
+        if opname in ("//", "/") and ka == "m" and kb == "m":
+            common = self._resolve(np.result_type, a.dtype, b.dtype)
+            x, y = self._to_unit(a, common), self._to_unit(b, common)
+            if opname == "//":
+                return _Typed(x + y + [OP["FLOORDIV_I"]], dt)
+            return _Typed(x + [OP["I2F"]] + y + [OP["I2F"], OP["DIV_F"]], dt)
+        raise UnsupportedExpression(f"{a.dtype} {opname} {b.dtype}")
+
     def _bitwise(self, opname, a, b):
         ufunc = {"&": np.bitwise_and, "|": np.bitwise_or, "^": np.bitwise_xor,
                  "<<": np.left_shift, ">>": np.right_shift}[opname]
@@ -275,6 +386,8 @@ class Compiler:
     def v_UnaryOp(self, node):
         a = self.visit(node.operand)
         if isinstance(node.op, ast.USub):
+            if a.dtype.kind == "M":
+                raise UnsupportedExpression("negation of a datetime")
             if a.scalar is not None:
                 return self._const(-a.scalar)
             if a.dtype.kind == "b":
@@ -287,8 +400,8 @@ class Compiler:
         if isinstance(node.op, (ast.Invert, ast.Not)):
             if a.dtype.kind == "b":
                 return _Typed(a.code + [OP["NOT_B"]], np.bool_)
-            if isinstance(node.op, ast.Not) or a.dtype.kind == "f":
-                raise UnsupportedExpression("not / ~ of a non-boolean float")
+            if isinstance(node.op, ast.Not) or a.dtype.kind in "fmM":  # numpy: no invert loop for them
+                raise UnsupportedExpression(f"not / ~ of {a.dtype}")
             return _Typed(self._finish(a.code + [OP["INV_I"]], a.dtype), a.dtype)
         raise UnsupportedExpression("unary operator")
 
@@ -302,6 +415,13 @@ class Compiler:
         def is_int(t):
             return t.scalar is not None and not isinstance(t.scalar, bool) and isinstance(t.scalar, int)
 
+        if a.dtype.kind in "mM" or b.dtype.kind in "mM":
+            if a.dtype.kind != b.dtype.kind:
+                raise UnsupportedExpression(f"comparison of {a.dtype} with {b.dtype}")
+            # like kinds meet in numpy's result unit; a column against a constant of its own
+            # unit stays COL CONST CMP, the shape of the comparison-terms kernel
+            common = self._resolve(np.result_type, a.dtype, b.dtype)
+            return _Typed(self._to_unit(a, common) + self._to_unit(b, common) + [OP[sym + "_I"]], np.bool_)
         # integers compare exactly in numpy 2, whatever the two dtypes
         if is_int(b) and a.scalar is None and a.dtype.kind in "iub":
             return self._compare_int_const(sym, a, b)
@@ -375,7 +495,29 @@ class Compiler:
             raise UnsupportedExpression("keyword arguments")
         if name == "astype" and len(node.args) == 2:
             return self._astype(node.args[0], node.args[1])
+        if name in ("datetime64", "timedelta64", "scalar_datetime", "scalar_timedelta"):
+            # np.datetime64('2015-06-01') (the repr of a numpy 2 scalar), functions.py:274-281
+            try:
+                values = [ast.literal_eval(a) for a in node.args]
+                make = np.datetime64 if name.endswith("datetime64") or name == "scalar_datetime" else np.timedelta64
+                return self._const(make(*values))
+            except (ValueError, TypeError) as e:
+                raise UnsupportedExpression(f"{name}: {e}")
         args = [self.visit(a) for a in node.args]
+        if name.startswith("dt_") and name[3:] in DT_FIELDS and len(args) == 1:
+            a = args[0]
+            if a.dtype.kind != "M" or a.scalar is not None or np.datetime_data(a.dtype)[0] not in DT_FIELD_UNITS:
+                raise UnsupportedExpression(f"{name} of {a.dtype} (a datetime64 expression in ns .. D)")
+            arg = DT_FIELDS.index(name[3:]) | _unit(a.dtype) << 4
+            return _Typed(a.code + [DT_OP["DT_FIELD"] | arg << 8], np.bool_ if name == "dt_is_leap_year" else np.int32)
+        if name.startswith("td_") and name[3:] in TD_FIELDS and len(args) == 1:
+            a = args[0]
+            if a.dtype.kind != "m" or a.scalar is not None or np.datetime_data(a.dtype)[0] not in DT_FIELD_UNITS:
+                raise UnsupportedExpression(f"{name} of {a.dtype} (a timedelta64 expression in ns .. D)")
+            field, dt = TD_FIELDS[name[3:]]
+            return _Typed(a.code + [DT_OP["TD_FIELD"] | (field | _unit(a.dtype) << 4) << 8], dt)
+        if any(a.dtype.kind in "mM" for a in args) and name not in ("minimum", "maximum", "where"):
+            raise UnsupportedExpression(f"function {name} of a datetime64 / timedelta64 value")
         if name in FUNCTIONS and len(args) == 1:
             ufunc, op = FUNCTIONS[name]
             a = args[0]
@@ -401,6 +543,11 @@ class Compiler:
             if name in ("fmin", "fmax"):
                 raise UnsupportedExpression(name)
             dt = self._resolve(getattr(np, name), a.proto, b.proto)
+            if dt.kind in "mM":
+                if a.dtype.kind != b.dtype.kind or name == "arctan2":
+                    raise UnsupportedExpression(f"{name} of {a.dtype} and {b.dtype}")
+                op = {"minimum": "MIN_I", "maximum": "MAX_I"}[name]
+                return _Typed(self._to_unit(a, dt) + self._to_unit(b, dt) + [OP[op]], dt)
             if dt.kind == "f":
                 op = {"minimum": "MIN_F", "maximum": "MAX_F", "arctan2": "ARCTAN2"}[name]
                 return _Typed(self._finish(self._to_float(a, dt) + self._to_float(b, dt) + [OP[op]], dt), dt)
@@ -417,7 +564,11 @@ class Compiler:
                 if dt.kind in "iu" and isinstance(t.scalar, int) and not isinstance(t.scalar, bool) \
                         and not np.iinfo(dt).min <= t.scalar <= np.iinfo(dt).max:
                     raise UnsupportedExpression(f"Python integer {t.scalar} out of bounds for {dt}")
-            if dt.kind == "f":
+            if dt.kind in "mM" or a.dtype.kind in "mM" or b.dtype.kind in "mM":
+                if a.dtype.kind != b.dtype.kind or dt.kind not in "mM":
+                    raise UnsupportedExpression(f"where of {a.dtype} and {b.dtype}")
+                code = c.code + self._to_unit(a, dt) + self._to_unit(b, dt) + [OP["WHERE"]]
+            elif dt.kind == "f":
                 code = c.code + self._to_float(a, dt) + self._to_float(b, dt) + [OP["WHERE"]]
             else:
                 code = c.code + a.code + b.code + [OP["WHERE"]]
@@ -434,9 +585,11 @@ class Compiler:
             dt = np.dtype(dtype_node.value)
         except TypeError as e:
             raise UnsupportedExpression(str(e))
-        if dt.kind not in "biuf" or dt.itemsize > 8:
+        if dt.kind not in "biufmM" or dt.itemsize > 8:
             raise UnsupportedExpression(f"astype to {dt}")
         a = self.visit(value_node)
+        if dt.kind in "mM" or a.dtype.kind in "mM":
+            return self._astype_time(a, dt)
         if a.dtype == dt and a.scalar is None:
             return a
         if a.scalar is not None:
@@ -456,6 +609,33 @@ class Compiler:
         # float -> uint64 reaches 2**64, beyond F2I's int64
         code = list(a.code) + ([OP["F2U" if dt == np.uint64 else "F2I"]] if a.dtype.kind == "f" else [])
         return _Typed(self._finish(code, dt), dt)
+
+
+    def _astype_time(self, a, dt):
+        """Unit casts of datetime64 / timedelta64 (DT_CAST: finer -> coarser floors, to M / Y
+        through the civil date, as numpy), and the reinterpreting casts to and from int64.
+        What numpy refuses (a timedelta64 cast across the M / Y boundary, datetime64 <->
+        timedelta64) is refused."""
+        if dt.kind in "mM":
+            _unit(dt)
+        with np.errstate(all="ignore"):
+            try:
+                np.empty(0, a.dtype).astype(dt)
+            except TypeError as e:
+                raise UnsupportedExpression(str(e))
+        if a.dtype.kind in "mM" and dt.kind in "mM":
+            if a.dtype.kind != dt.kind or (dt.kind == "m" and (_unit(a.dtype) >= 8) != (_unit(dt) >= 8)):
+                raise UnsupportedExpression(f"astype of {a.dtype} to {dt}")  # numpy: no m8 cast across M / Y
+            if a.scalar is not None:
+                return _Typed(self._to_unit(a, dt), dt, scalar=a.scalar.astype(dt))
+            return _Typed(self._to_unit(a, dt), dt)
+        if (a.dtype.kind in "mM" and dt == np.int64) or (dt.kind in "mM" and a.dtype == np.int64 and
+                                                        not isinstance(a.scalar, bool)):
+            if a.scalar is not None:
+                v = np.asarray(a.scalar).astype(dt)[()]
+                return self._const(v) if dt.kind in "mM" else _Typed(self._const(int(v)).code, dt)
+            return _Typed(list(a.code), dt)  # the ticks themselves
+        raise UnsupportedExpression(f"astype of {a.dtype} to {dt}")
 
 
 def _stack_depth(code):
@@ -540,6 +720,10 @@ def compile_expression(df, expression):
            tuple(sorted((k, repr(v)) for k, v in df.variables.items() if np.isscalar(v))),
            tuple((k, str(getattr(v, "dtype", ""))) for k, v in df.columns.items()))
     p = _CACHE.get(key)
+    if p is not None:
+        for name in p.columns:  # the key names dtypes, not column objects: a new column may hold NaT
+            if np.dtype(df.columns[name].dtype).kind in "mM" and df._column_has_nat(name):
+                raise UnsupportedExpression(f"column {name!r} holds NaT (not-a-time) values")
     if p is None:
         p = Program(df, expression)
         if len(_CACHE) > 256:

@@ -23,6 +23,59 @@ class BinnerBase:
     pass
 
 
+class BinnerTime(BinnerBase):
+    """groupby.py:30-94: bins a datetime expression in a datetime resolution (numpy unit
+    ``resolution``, ``every`` of them per bin).  Unlike :class:`Grouper`, every bin between
+    the minimum and the maximum is present in the result, also the empty ones; the label
+    column is ``datetime64[resolution]``.  The bin of a row is
+    ``astype(astype(t, 'M8[R]') - t_begin, 'int') // every`` with ``t_begin`` the minimum in
+    that resolution, a variable added to the frame; on an HBM frame the device expression
+    kernel evaluates it (numpy's flooring casts, expr.py).
+
+    >>> t = np.arange('2015-01-01', '2015-02-01', dtype=np.datetime64)
+    >>> df = vaex_amd.from_arrays(t=t, y=np.arange(len(t)))
+    >>> df.groupby(vaex_amd.BinnerTime.per_week(df.t), agg={'y': 'sum'})  # y: 21 70 119 168 87
+    """
+
+    def __init__(self, expression, resolution="W", df=None, every=1):
+        self.resolution = resolution
+        self.df = df if df is not None else expression.df
+        self.sort_indices = None
+        self.expression = self.df[str(expression)]
+        self.label = str(self.expression)
+        self.tmin, self.tmax = self.expression.minmax()
+        self.resolution_type = "M8[%s]" % self.resolution
+        tmin, tmax = self.tmin.astype(self.resolution_type), self.tmax.astype(self.resolution_type)
+        self.N = (tmax - tmin).astype(int).item() + 1
+        self.N = (self.N + every - 1) // every  # divide by every, and round up
+        self.bin_values = np.arange(tmin, tmax + 1, every)
+        self.begin_name = self.df.add_variable("t_begin", tmin, unique=True)
+        self.binby_expression = "(astype((astype(%s, %r) - %s), 'int64') // %d)" % (
+            self.expression, str(np.dtype(self.resolution_type)), self.begin_name, every)
+        self.binner = self.df._binner_ordinal(self.binby_expression, self.N)
+        self.expression = self.binby_expression  # what GroupByBase bins by
+
+    @classmethod
+    def per_day(cls, expression, df=None):
+        return cls(expression, "D", df)
+
+    @classmethod
+    def per_week(cls, expression, df=None):
+        return cls(expression, "W", df)
+
+    @classmethod
+    def per_month(cls, expression, df=None):
+        return cls(expression, "M", df)
+
+    @classmethod
+    def per_quarter(cls, expression, df=None, every=1):
+        return cls(expression, "M", df, every=3 * every)
+
+    @classmethod
+    def per_year(cls, expression, df=None):
+        return cls(expression, "Y", df)
+
+
 class Grouper(BinnerBase):
     def __init__(self, expression, df=None, sort=False, pre_sort=True, row_limit=None, df_original=None):
         self.df = df if df is not None else expression.df
