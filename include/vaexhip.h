@@ -481,6 +481,50 @@ int vh_argsort(int nkeys, const void *const *keys, const int *dtypes, uint64_t n
 int vh_decode_keys(uint64_t n, const int64_t *ck, const int64_t *table, int nkeys, const int64_t *mins,
                    const int64_t *mults, const int64_t *spans, const int *itemsizes, void *const *outs);
 
+/* ---- string columns in HBM (strings.hip) -------------------------------------------
+ * A string column is the Arrow layout: n + 1 offsets (int32 or int64, off_itemsize 4 or 8) into
+ * a byte buffer.  The byte buffer's allocation starts 8-aligned and carries at least 16 bytes
+ * after its last byte; a slice passes its own offsets pointer and the parent's bytes.  Every
+ * entry but the check itself takes offsets that passed it.
+ *
+ * The check: *bad = 0 when the n + 1 offsets are non-negative, non-decreasing and the last is
+ * at most nbytes; else bit 0: a negative offset, bit 1: a decreasing pair, bit 2: the last
+ * offset past the buffer.  Reads no bytes. */
+int vh_str_validate(const void *offsets, int off_itemsize, uint64_t n, uint64_t nbytes, int *bad);
+/* out[i] = the length of row i in bytes (kind 0) or in UTF-8 code points (kind 1: the bytes
+ * that are not 10xxxxxx) */
+int vh_str_len(const void *offsets, int off_itemsize, const uint8_t *bytes, uint64_t n, int kind, int64_t *out);
+/* out[i] = 0 / 1: row i against a literal pattern (a host buffer of at most 1024 bytes).
+ * op 0: equal, 1: not equal, 2: starts with, 3: ends with, 4: contains (an empty pattern is
+ * contained in every string) */
+int vh_str_match(const void *offsets, int off_itemsize, const uint8_t *bytes, uint64_t n, int op, const uint8_t *pattern,
+                 uint64_t pattern_len, uint8_t *out);
+/* The gather column[indices] in two calls, so that the caller can size the output in between.
+ * The plan: pos[0 .. m] (HBM) = the exclusive scan of the taken rows' byte lengths, *total the
+ * sum.  indices: m row numbers (HBM, int32 or int64) of a column of n rows; a row number outside
+ * [0, n) takes the empty string. */
+int vh_str_take_plan(const void *offsets, int off_itemsize, uint64_t n, const void *indices, int idx_itemsize, uint64_t m,
+                     uint64_t *pos, uint64_t *total);
+/* the copy: out_offsets (m + 1 of out_itemsize bytes; 4 only while total < 2^31) and out_bytes
+ * (total bytes + 16 of slack) from the plan */
+int vh_str_take(const void *offsets, int off_itemsize, const uint8_t *bytes, uint64_t n, const void *indices,
+                int idx_itemsize, uint64_t m, const uint64_t *pos, uint64_t total, void *out_offsets, int out_itemsize,
+                uint8_t *out_bytes);
+/* The dictionary encoder (superutils.ordered_set_string): the distinct strings of the columns
+ * it has seen, numbered in first-appearance order, kept in a dictionary of its own in HBM.
+ * hash_bits (0 .. 64): the low bits of the 64-bit hash that the slot tables key on; fewer than
+ * 64 forces collisions, which the encoder resolves exactly (a test seam).  initial_capacity:
+ * slots of a fresh table, 0 for the default. */
+int vh_strset_create(int hash_bits, uint64_t initial_capacity, void **out);
+int vh_strset_destroy(void *set);
+/* add the strings of n < 2^32 rows */
+int vh_strset_update(void *set, const void *offsets, int off_itemsize, const uint8_t *bytes, uint64_t n);
+int vh_strset_info(void *set, int64_t *count, int64_t *dict_bytes, int64_t *levels, int64_t *table_bytes);
+/* the dictionary to the host: count + 1 offsets and dict_bytes bytes */
+int vh_strset_dict(void *set, int64_t *offsets_out, uint8_t *bytes_out);
+/* out[i] (HBM, int32) = the ordinal of row i, -1 for a string the set does not hold */
+int vh_strset_map_ordinal(void *set, const void *offsets, int off_itemsize, const uint8_t *bytes, uint64_t n, int32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ reference's plugin surface for that path:
 * :mod:`vaex_amd.expr`       -- expressions / selections / filters evaluated on the GPU
 * :mod:`vaex_amd.selections` -- ``vaex.selections`` (modes, history nodes, the lasso)
 * :mod:`vaex_amd.datetime`   -- ``dt_*`` / ``td_*`` functions and the ``.dt`` / ``.td`` accessors
+* :mod:`vaex_amd.strings`    -- string columns in HBM, ``ordered_set_string``, the ``str_*`` kernels
 """
 from . import _lib  # noqa: F401  (fails loudly if the HIP library is missing)
 from . import agg, superagg, superutils  # noqa: F401
@@ -21,6 +22,7 @@ from .dataframe import DataFrame, Expression, RowLimitException, from_arrays, fr
 from .device import DeviceArray  # noqa: F401
 from .execution import ExecutorLocal, default_executor  # noqa: F401
 from .groupby import BinnerTime  # noqa: F401
+from .strings import DeviceStringArray  # noqa: F401
 
 __version__ = "0.1.0"
 

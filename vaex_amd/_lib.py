@@ -135,6 +135,17 @@ SIGNATURES = {
     "vh_pnpoly": (_i32, [_vp, _i32, _vp, _i32, _u64, _p(_dbl), _p(_dbl), _i32, _dbl, _dbl, _dbl, _vp, _i32, _vp]),
     "vh_mask_combine": (_i32, [_vp, _vp, _i32, _u64, _vp]),
     "vh_expr_eval": (_i32, [_p(ctypes.c_uint32), _i32, _p(_u64), _i32, _p(_vp), _p(_i32), _i32, _u64, _i32, _vp]),
+    "vh_str_validate": (_i32, [_vp, _i32, _u64, _u64, _p(_i32)]),
+    "vh_str_len": (_i32, [_vp, _i32, _vp, _u64, _i32, _vp]),
+    "vh_str_match": (_i32, [_vp, _i32, _vp, _u64, _i32, ctypes.c_char_p, _u64, _vp]),
+    "vh_str_take_plan": (_i32, [_vp, _i32, _u64, _vp, _i32, _u64, _vp, _p(_u64)]),
+    "vh_str_take": (_i32, [_vp, _i32, _vp, _u64, _vp, _i32, _u64, _vp, _u64, _vp, _i32, _vp]),
+    "vh_strset_create": (_i32, [_i32, _u64, _p(_vp)]),
+    "vh_strset_destroy": (_i32, [_vp]),
+    "vh_strset_update": (_i32, [_vp, _vp, _i32, _vp, _u64]),
+    "vh_strset_info": (_i32, [_vp, _p(_i64), _p(_i64), _p(_i64), _p(_i64)]),
+    "vh_strset_dict": (_i32, [_vp, _vp, _vp]),
+    "vh_strset_map_ordinal": (_i32, [_vp, _vp, _i32, _vp, _u64, _vp]),
 }
 
 _lib = None

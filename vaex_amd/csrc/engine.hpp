@@ -240,6 +240,8 @@ void note_host_image_bin();
 // row0 + j); false when not eligible or when its resolve list overflowed (scratch reset)
 bool try_tiled_first(const BinPlan &plan, const AggDev &ad, uint64_t n, uint64_t cells, uint64_t row0, int nd_f64);
 uint64_t stat_first_tiled(bool reset);  // chunks binned by try_tiled_first
+uint64_t stat_strset_rounds(bool reset);  // strings.hip: the most rounds an encoder update took
+uint64_t stat_strset_form(bool reset);    // strings.hip: the last row-kernel form (0 lane, 1 wave per row)
 // a set-ordinal grid (one set-ordinal binner over an integer key) with count / float64 sum
 // aggregators through the fused hash aggregation (hashagg.hip); false when not eligible
 bool hashagg_bin_set_ordinal(const BinPlan &plan, const FusedAggs &fa, uint64_t n);

@@ -813,6 +813,8 @@ int vh_stat_read(const char *name, uint64_t *value, int reset) {
     else if (n == "hashagg_overflow_rows") *value = stat_hashagg_overflow(reset != 0);
     else if (n == "set_overflow_rows") *value = stat_set_overflow(reset != 0);
     else if (n == "first_tiled_chunks") *value = stat_first_tiled(reset != 0);
+    else if (n == "strset_rounds") *value = stat_strset_rounds(reset != 0);
+    else if (n == "strset_form") *value = stat_strset_form(reset != 0);
     else fail(VH_ERR_ARG, "vh_stat_read: unknown statistic '" + n + "'");
     VH_API_END
 }

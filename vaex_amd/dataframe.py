@@ -24,6 +24,7 @@ import numpy as np
 from . import agg as vagg
 from . import selections
 from .device import DeviceArray
+from .strings import STRING, DeviceStringArray
 from .execution import default_executor
 from .promise import Promise, delayed
 from .tasks import TaskMinMax, TaskSetCreate, TaskValueCounts
@@ -143,8 +144,16 @@ class Expression:
     def __le__(self, o): return self._binop(o, "<=")
     def __gt__(self, o): return self._binop(o, ">")
     def __ge__(self, o): return self._binop(o, ">=")
-    def __eq__(self, o): return self._binop(o, "==")
-    def __ne__(self, o): return self._binop(o, "!=")
+    def __eq__(self, o):
+        if isinstance(o, str):  # functions.py str_equals: a string column against a literal
+            return Expression(self.df, f"str_equals({self.expression}, {o!r})")
+        return self._binop(o, "==")
+
+    def __ne__(self, o):
+        if isinstance(o, str):
+            return Expression(self.df, f"str_notequals({self.expression}, {o!r})")
+        return self._binop(o, "!=")
+
     def __and__(self, o): return self._binop(o, "&")
     def __or__(self, o): return self._binop(o, "|")
     def __neg__(self): return Expression(self.df, f"(-{self.expression})")
@@ -172,12 +181,18 @@ class Expression:
         return TimeDelta(self)
 
     @property
+    def str(self):
+        """expression.py ``StringOperations`` accessor: ``df.s.str.contains('x')`` is
+        ``str_contains(s, 'x')`` (strings.py; the device string kernels)."""
+        return StringOperations(self)
+
+    @property
     def values(self):
         return self.df.evaluate(self.expression)
 
     def to_numpy(self):
         v = self.values
-        if isinstance(v, DeviceArray):
+        if isinstance(v, (DeviceArray, DeviceStringArray)):
             return v.to_numpy()
         return v if np.ma.isMaskedArray(v) else np.asarray(v)  # masked columns stay masked
 
@@ -213,6 +228,29 @@ class Expression:
         if isinstance(keys, Promise):
             return keys.then(len)
         return len(keys)
+
+
+class StringOperations:
+    """``Expression.str``: the string functions that run on the device, each as the reference's
+    function form (``functions.py`` ``str_*``) over the expression's text."""
+
+    def __init__(self, expression):
+        self.expression = expression
+
+    def _call(self, name, *args):
+        e = self.expression
+        return Expression(e.df, f"{name}({', '.join([e.expression] + [repr(a) for a in args])})")
+
+    def len(self): return self._call("str_len")
+    def byte_length(self): return self._call("str_byte_length")
+    def equals(self, other): return self._call("str_equals", other)
+    def startswith(self, pat): return self._call("str_startswith", pat)
+    def endswith(self, pat): return self._call("str_endswith", pat)
+
+    def contains(self, pat, regex=False):
+        if regex:
+            raise NotImplementedError("str.contains: regular expressions are not supported (regex=False)")
+        return self._call("str_contains", pat)
 
 
 def _ordinal_values(x, ordered_set):
@@ -267,7 +305,11 @@ class DataFrame:
         return self._filter is not None
 
     def is_device_resident(self):
-        return any(isinstance(c, DeviceArray) for c in self.columns.values())
+        return any(isinstance(c, (DeviceArray, DeviceStringArray)) for c in self.columns.values())
+
+    def _is_string(self, expression):
+        """Whether the expression names a string column (strings.DeviceStringArray)."""
+        return isinstance(self.columns.get(str(expression)), DeviceStringArray)
 
     def get_column_names(self):
         return list(self.columns) + list(self.virtual_columns)
@@ -364,7 +406,7 @@ class DataFrame:
             filter_mask = None
         if expression in self.columns:
             col = self.columns[expression]
-            if isinstance(col, DeviceArray):
+            if isinstance(col, (DeviceArray, DeviceStringArray)):
                 if filter_mask is not None:
                     raise NotImplementedError("filtered DataFrames need host columns")
                 return col[i1:i2]
@@ -412,6 +454,9 @@ class DataFrame:
             # the filtered rows of an HBM frame: an HBM value is compacted on the device
             # (mask_rows + vh_take) and only the kept rows are read back
             v = self._eval_host(expression, i1, i2)
+            if isinstance(v, DeviceStringArray):
+                from .superutils import mask_rows
+                return v.take(mask_rows(fm)).to_numpy()
             if isinstance(v, DeviceArray):
                 from .sort import compact_device
                 return compact_device(v, fm).to_numpy()
@@ -473,6 +518,8 @@ class DataFrame:
 
     def data_type(self, expression):
         expression = str(expression)
+        if self._is_string(expression):
+            return STRING
         if expression in self.columns:
             return np.dtype(self.columns[expression].dtype)
         if self.is_device_resident():
@@ -968,6 +1015,10 @@ class DataFrame:
         binners = self._create_binners(binby, limits, shape, selection=sel)
         results = []
         for expr in expressions:
+            if self._is_string(expr):
+                if name != "count":  # a string column has no nulls: its count is the row count
+                    raise TypeError(f"{name} of the string column {expr!r}: numeric aggregators take numbers")
+                expr = "*"
             if expr in ("*", None):
                 aggd = vagg.aggregates[name](selection=sel, edges=edges)
             elif extra_expressions:
@@ -1137,6 +1188,8 @@ class DataFrame:
         if dropna:
             dropnan = dropmissing = True
         expression = _ensure_string(expression)
+        if self._is_string(expression):
+            return self._delay(delay, self._string_value_counts(expression, ascending, selection))
         dtype = self._key_dtype(expression)
         task = self.executor.schedule(TaskValueCounts(self, expression, selection=selection))
 
@@ -1171,6 +1224,8 @@ class DataFrame:
         if array_type not in ("python", "list", "numpy", None):
             raise ValueError(f"unknown array_type {array_type!r}")
         expression = _ensure_string(expression)
+        if self._is_string(expression):
+            return self._delay(delay, self._string_unique(expression, return_inverse, selection, array_type))
         dtype = self._key_dtype(expression)
         task = self._set(expression, progress=progress, selection=selection, flatten=axis is None, delay=True)
 
@@ -1207,11 +1262,75 @@ class DataFrame:
 
         return self._delay(delay, finish(task))
 
+    # ---- string keys ---------------------------------------------------------------
+    def _encoded(self, names):
+        """(frame, {hidden column: dictionary keys}): a copy in which each string column in
+        ``names`` has a hidden int32 column of its first-appearance codes beside it (the
+        dictionary encoder, strings.encode), named ``__str_<name>``.  Codes are kept per live
+        column object."""
+        from .strings import encode
+        df = self.copy()
+        cache = self.__dict__.setdefault("_string_codes", {})
+        keys = {}
+        for name in names:
+            col = self.columns[name]
+            hit = cache.get(name)
+            if hit is None or hit[0] is not col:
+                codes, sset = encode(col)
+                hit = cache[name] = (col, codes, sset.key_array())
+            hidden = f"__str_{name}"
+            df.columns[hidden] = hit[1]
+            keys[hidden] = hit[2]
+        return df, keys
+
+    def _string_value_counts(self, expression, ascending, selection):
+        """value_counts of a string column: the column is encoded, the codes are counted by the
+        integer counter, and the order is the numeric rule's (keys ascending bytewise, then a
+        stable sort by count; descending is the exact reverse)."""
+        from pandas import Series
+        from .strings import bytewise_order
+        df, keys = self._encoded([expression])
+        (hidden, keys), = keys.items()
+        order = bytewise_order(keys)
+        rank = np.empty(len(keys), np.int64)
+        rank[order] = np.arange(len(keys))
+        counts = df.value_counts(hidden, ascending=ascending, selection=selection)
+        codes = counts.index.to_numpy()
+        # the counter ordered the codes numerically; the rule orders the strings
+        pos = np.argsort(rank[codes], kind="stable")
+        c = counts.to_numpy()[pos]
+        codes = codes[pos]
+        by_count = np.argsort(c, kind="stable")
+        if not ascending:
+            by_count = by_count[::-1]
+        return Series(c[by_count], index=keys[codes[by_count]], dtype=np.int64)
+
+    def _string_unique(self, expression, return_inverse, selection, array_type):
+        """unique of a string column: the first-appearance order of the kept rows' codes."""
+        df, keys = self._encoded([expression])
+        (hidden, keys), = keys.items()
+        codes = np.asarray(df.unique(hidden, selection=selection, array_type="numpy"), dtype=np.int64)
+        out = keys[codes]
+        if array_type in ("python", "list"):
+            out = out.tolist()
+        if not return_inverse:
+            return out
+        # every (unfiltered) row's position in `out`; -1 for a row whose string only rows outside
+        # the filter / selection hold, as the numeric route's map_ordinal through the kept set
+        position = np.full(len(keys), -1, np.int64)
+        position[codes] = np.arange(len(codes))
+        return out, position[df.columns[hidden].to_numpy()]
+
     # ---- groupby -----------------------------------------------------------------
     def groupby(self, by=None, agg=None, sort=False, assume_sparse="auto", row_limit=None, copy=True,
                 progress=None, delay=False, _speculate=True):
         """dataframe.py:6622-6683."""
         from .groupby import DenseRangeMiss, GroupBy, GroupByDeferred, _dense_range, groupby_multikey, parse_actions
+        bys = [_ensure_string(b) for b in (by if isinstance(by, (list, tuple)) else [by])]
+        if agg is not None and any(self._is_string(b) for b in bys):
+            from .groupby import groupby_string_keys
+            return groupby_string_keys(self, bys, isinstance(by, (list, tuple)), agg, sort=sort,
+                                       assume_sparse=assume_sparse, row_limit=row_limit)
         if agg is None:  # df.groupby(by).agg(...): the same routes as groupby(by, agg=...)
             return GroupByDeferred(self, by, sort=sort, assume_sparse=assume_sparse, row_limit=row_limit)
         dense_ranges = {}
@@ -1385,7 +1504,7 @@ def from_arrays(**arrays):
     """vaex.from_arrays: numpy arrays (host) or DeviceArray (HBM-resident) columns."""
     cols = {}
     for k, v in arrays.items():
-        if isinstance(v, DeviceArray) or np.ma.isMaskedArray(v):
+        if isinstance(v, (DeviceArray, DeviceStringArray)) or np.ma.isMaskedArray(v):
             cols[k] = v
         else:
             cols[k] = np.asarray(v)

@@ -173,8 +173,34 @@ class Compiler:
         idx = self.consts.index(bits)
         return _Typed([OP["CONST"] | idx << 8], dt, scalar=value if not isinstance(value, np.generic) else value.item())
 
+    def _string_column(self, node):
+        """the name of the string column (strings.DeviceStringArray) an ast node names, else None"""
+        from .strings import DeviceStringArray
+        if isinstance(node, ast.Name) and isinstance(self.df.columns.get(node.id), DeviceStringArray):
+            return node.id
+        return None
+
+    def _string_input(self, fn, name, arg=None):
+        """A string function of a string column (``str_*``, strings.py) as one more input column
+        of the program: the string kernel fills it for the rows [i1, i2) at evaluate time
+        (Program.evaluate), a bool mask for the predicates, int64 for the lengths."""
+        from . import strings
+        if fn in strings.MATCH_OPS:
+            if not isinstance(arg, str):
+                raise UnsupportedExpression(f"{fn}: the pattern is a str constant")
+            strings._pattern(arg)  # NotImplementedError past 1024 bytes
+        key = ("str", fn, name, arg)
+        if key not in self.columns:
+            if len(self.columns) >= MAX_COLS:
+                raise UnsupportedExpression("too many columns")
+            self.columns.append(key)
+        return _Typed([OP["COL"] | self.columns.index(key) << 8], np.int64 if fn in strings.LEN_KINDS else np.bool_)
+
     def _column(self, name):
         col = self.df.columns[name]
+        if self._string_column(ast.Name(id=name)):
+            raise UnsupportedExpression(f"string column {name!r}: strings compute through str_* functions and "
+                                        "comparisons with a str constant")
         dt = np.dtype(col.dtype)
         if dt.kind not in "biufmM" or not dt.isnative:
             raise UnsupportedExpression(f"column {name!r} of dtype {dt}")
@@ -464,6 +490,14 @@ class Compiler:
         return _Typed(s.code + zero + [OP[first]] + s.code + u.code + [OP[second], OP[comb]], np.bool_)
 
     def v_Compare(self, node):
+        if len(node.ops) == 1 and isinstance(node.ops[0], (ast.Eq, ast.NotEq)):
+            # string column == / != 'constant' (either side): str_equals / str_notequals
+            a, b = node.left, node.comparators[0]
+            for col, con in ((a, b), (b, a)):
+                name = self._string_column(col)
+                if name and isinstance(con, ast.Constant) and isinstance(con.value, str):
+                    return self._string_input("str_equals" if isinstance(node.ops[0], ast.Eq) else "str_notequals",
+                                              name, con.value)
         left = self.visit(node.left)
         out = None
         for op, comp in zip(node.ops, node.comparators):
@@ -491,6 +525,9 @@ class Compiler:
             name = f.id
         else:
             raise UnsupportedExpression("call")
+        from . import strings
+        if name in strings.FUNCTIONS:
+            return self._string_call(name, node)
         if node.keywords:
             raise UnsupportedExpression("keyword arguments")
         if name == "astype" and len(node.args) == 2:
@@ -574,6 +611,32 @@ class Compiler:
                 code = c.code + a.code + b.code + [OP["WHERE"]]
             return _Typed(self._finish(code, dt), dt)
         raise UnsupportedExpression(f"function {name}")
+
+    def _string_call(self, name, node):
+        """``str_len(s)`` / ``str_byte_length(s)`` / ``str_<predicate>(s, 'literal')`` over a string
+        column (``str_contains`` also with ``regex=False`` or a third positional False)."""
+        from . import strings
+        col = self._string_column(node.args[0]) if node.args else None
+        if col is None:
+            raise UnsupportedExpression(f"{name} takes a string column")
+        rest = list(node.args[1:])
+        if name == "str_contains":
+            flags = [k.value for k in node.keywords if k.arg == "regex"] + rest[1:2]
+            if len(flags) > 1 or len(node.keywords) > len(flags) or len(rest) > 2:
+                raise UnsupportedExpression("str_contains(s, pattern, regex=False)")
+            for f in flags:
+                if not (isinstance(f, ast.Constant) and f.value is False):
+                    raise NotImplementedError("str_contains: regular expressions are not supported (regex=False)")
+            rest = rest[:1]
+        elif node.keywords:
+            raise UnsupportedExpression("keyword arguments")
+        if name in strings.LEN_KINDS:
+            if rest:
+                raise UnsupportedExpression(f"{name} takes one argument")
+            return self._string_input(name, col)
+        if len(rest) != 1 or not isinstance(rest[0], ast.Constant):
+            raise UnsupportedExpression(f"{name}(s, 'literal')")
+        return self._string_input(name, col, rest[0].value)
 
     def _astype(self, value_node, dtype_node):
         """``astype(x, 'dtype')`` (the reference's ``Expression.astype``, expression.py;
@@ -690,6 +753,11 @@ class Program:
         cols = []
         keep = []
         for name in self.columns:
+            if isinstance(name, tuple):  # a string function's column (Compiler._string_input)
+                _, fn, cname, arg = name
+                scol = df.columns[cname][i1:i2]
+                cols.append(scol.match(fn, arg) if arg is not None else scol.len(fn))
+                continue
             col = df.columns[name]
             if not isinstance(col, DeviceArray):
                 col = DeviceArray.from_numpy(np.ascontiguousarray(col[i1:i2]))
@@ -722,6 +790,8 @@ def compile_expression(df, expression):
     p = _CACHE.get(key)
     if p is not None:
         for name in p.columns:  # the key names dtypes, not column objects: a new column may hold NaT
+            if isinstance(name, tuple):
+                continue
             if np.dtype(df.columns[name].dtype).kind in "mM" and df._column_has_nat(name):
                 raise UnsupportedExpression(f"column {name!r} holds NaT (not-a-time) values")
     if p is None:

@@ -675,6 +675,37 @@ def parse_actions(df, actions, groupby_expression):
     return out
 
 
+def groupby_string_keys(df, bys, multikey, agg, sort=False, assume_sparse="auto", row_limit=None):
+    """groupby with string columns among the keys (strings.py): on a copy of the frame each
+    string key becomes a hidden int32 column of its first-appearance codes (the dictionary
+    encoder), the integer routes run on it, and the result's label column is decoded through the
+    dictionary.  sort=True: the dictionary's distinct strings are ordered on the host (bytewise,
+    Python's ``str`` order) and the codes are remapped to their ranks on the device, so the
+    integer order is the string order.  Without sort a single string key's groups come in
+    first-appearance order: that is the order of its codes."""
+    from .strings import rank_codes
+    names = [b for b in bys if df._is_string(b)]
+    edf, keys = df._encoded(names)
+    tables = {}
+    for name in names:
+        hidden = f"__str_{name}"
+        table = keys[hidden]
+        if sort:
+            edf.columns[hidden], order = rank_codes(edf.columns[hidden], table)
+            table = table[np.asarray(order, dtype=np.int64)]
+        tables[hidden] = table
+    hidden_by = [f"__str_{b}" if b in names else b for b in bys]
+    res = edf.groupby(hidden_by if multikey else hidden_by[0], agg=agg, sort=sort, assume_sparse=assume_sparse,
+                      row_limit=row_limit)
+    columns = {}
+    for k, v in res.columns.items():
+        if k in tables:
+            columns[k[len("__str_"):]] = tables[k][np.asarray(v).astype(np.int64)]
+        else:
+            columns[k] = v
+    return DataFrame(columns)
+
+
 class GroupBy(GroupByBase):
     def agg(self, actions):
         """groupby.py:484-533."""
@@ -859,6 +890,10 @@ class GroupByDeferred:
     def _groupby(self):
         if self._real is None:
             kw = self._kw
+            bys = self._by if isinstance(self._by, (list, tuple)) else [self._by]
+            if any(self._df._is_string(b) for b in bys):
+                # the groupers read numeric keys; a string key is encoded by the agg route only
+                raise NotImplementedError("groupby by a string key: only .agg(...) / groupby(by, agg=...) is supported")
             self._real = GroupBy(self._df, by=self._by, sort=kw["sort"], row_limit=kw["row_limit"],
                                  dense=kw["assume_sparse"] != True)  # noqa: E712
         return self._real

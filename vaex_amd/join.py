@@ -79,8 +79,16 @@ def gather(columns, lookup, length, masked=False):
     back as a host ``np.ma`` array with those rows masked (an HBM column is read back together
     with the mask the gather kernel wrote)."""
     out = {}
+    from .strings import DeviceStringArray
     dev_names = [k for k, c in columns.items() if isinstance(c, DeviceArray)]
-    host_names = [k for k in columns if k not in dev_names]
+    str_names = [k for k, c in columns.items() if isinstance(c, DeviceStringArray)]
+    host_names = [k for k in columns if k not in dev_names and k not in str_names]
+    if str_names:  # string columns: the byte-exact device gather (vh_str_take)
+        if masked:
+            raise NotImplementedError("string columns carry no nulls: a gather that leaves rows unmatched")
+        dl = _device_indices(lookup, length)
+        for k in str_names:
+            out[k] = columns[k].take(dl)
     if dev_names:
         dl = _device_indices(lookup, length)
         cols = [columns[k] for k in dev_names]  # vh_take launches once per eight columns

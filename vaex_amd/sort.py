@@ -12,6 +12,7 @@ import numpy as np
 
 from .device import DeviceArray
 from .join import _chunks, _host_indices, take_rows
+from .strings import DeviceStringArray, encode, rank_codes
 from .superutils import argsort_device, mask_rows, take_device
 
 
@@ -52,6 +53,13 @@ def _host_order(keys, rows, ascending, single):
     return order if rows is None else rows[order]
 
 
+def _string_ranks(column):
+    """A string key as an int32 column that sorts like it: the rank of each row's string among
+    the column's distinct strings (the encoder's codes remapped, strings.rank_codes)."""
+    codes, sset = encode(column)
+    return rank_codes(codes, sset.key_array())[0]
+
+
 def argsort(df, by, ascending=True):
     """The unfiltered row numbers of the rows ``df`` keeps, in the order of ``by`` (an
     expression, or a list / tuple of them with the first the most significant): stable, NaN
@@ -62,6 +70,7 @@ def argsort(df, by, ascending=True):
         raise ValueError("sort needs at least one key")
     n = _rows(df)
     keys = [df._eval_host(b, 0, n) for b in bys]
+    keys = [_string_ranks(k) if isinstance(k, DeviceStringArray) else k for k in keys]
     rows = kept_rows(df) if df.filtered else None
     if not df.is_device_resident() or any(np.ma.isMaskedArray(k) for k in keys):
         return _host_order(keys, rows, ascending, single)
