@@ -510,6 +510,29 @@ int vh_str_take_plan(const void *offsets, int off_itemsize, uint64_t n, const vo
 int vh_str_take(const void *offsets, int off_itemsize, const uint8_t *bytes, uint64_t n, const void *indices,
                 int idx_itemsize, uint64_t m, const uint64_t *pos, uint64_t total, void *out_offsets, int out_itemsize,
                 uint8_t *out_bytes);
+/* String-producing functions of a column, in two calls like the gather: the
+ * plan writes pos[0 .. n] (HBM), the exclusive scan of the rows' result lengths, and *total;
+ * the write fills out_offsets (n + 1 of out_itemsize bytes; 4 only while total < 2^31) and
+ * out_bytes (total bytes + 16 of slack).  Both calls take the same op and parameters.
+ * op 0: lower, 1: upper (flags 1: ASCII letters only; else table holds ntable <= 2048 pairs
+ * (code point, image), sorted, none below 128: the host's case table), 2: slice [a, b) in code
+ * points (flags 1: b is given), 3: strip the ASCII bytes c0[0 .. n0) (flags 1: left, 2: right,
+ * 3: both), 4: pad to a code points with the byte c0[0] (flags as strip: the side(s) that grow),
+ * 5: repeat a times, 6: cat with the constant c0 (flags 1: the constant first) or with the same
+ * row of a second column (offsets2 / bytes2, flags 2), 7: replace c0 (not empty) by c1, at most
+ * a times (a < 0: all).  Constants are host buffers of at most 1024 bytes; offsets2 is NULL
+ * unless op is 6 with flags 2.  Repeats and widths are any int64: when a row's result, or the
+ * sum, cannot fit (a row above 2^62 / (n + 1) bytes) the plan sets *total to
+ * VH_STR_FN_TOO_LONG, and no write may follow. */
+#define VH_STR_FN_TOO_LONG UINT64_MAX
+int vh_str_fn_plan(const void *offsets, int off_itemsize, const uint8_t *bytes, uint64_t n, const void *offsets2,
+                   int off2_itemsize, const uint8_t *bytes2, int op, int64_t a, int64_t b, int flags, const uint8_t *c0,
+                   uint64_t n0, const uint8_t *c1, uint64_t n1, const uint32_t *table, uint64_t ntable, uint64_t *pos,
+                   uint64_t *total);
+int vh_str_fn(const void *offsets, int off_itemsize, const uint8_t *bytes, uint64_t n, const void *offsets2, int off2_itemsize,
+              const uint8_t *bytes2, int op, int64_t a, int64_t b, int flags, const uint8_t *c0, uint64_t n0,
+              const uint8_t *c1, uint64_t n1, const uint32_t *table, uint64_t ntable, const uint64_t *pos, uint64_t total,
+              void *out_offsets, int out_itemsize, uint8_t *out_bytes);
 /* The dictionary encoder (superutils.ordered_set_string): the distinct strings of the columns
  * it has seen, numbered in first-appearance order, kept in a dictionary of its own in HBM.
  * hash_bits (0 .. 64): the low bits of the 64-bit hash that the slot tables key on; fewer than

@@ -140,6 +140,10 @@ SIGNATURES = {
     "vh_str_match": (_i32, [_vp, _i32, _vp, _u64, _i32, ctypes.c_char_p, _u64, _vp]),
     "vh_str_take_plan": (_i32, [_vp, _i32, _u64, _vp, _i32, _u64, _vp, _p(_u64)]),
     "vh_str_take": (_i32, [_vp, _i32, _vp, _u64, _vp, _i32, _u64, _vp, _u64, _vp, _i32, _vp]),
+    "vh_str_fn_plan": (_i32, [_vp, _i32, _vp, _u64, _vp, _i32, _vp, _i32, _i64, _i64, _i32, ctypes.c_char_p, _u64,
+                              ctypes.c_char_p, _u64, _vp, _u64, _vp, _p(_u64)]),
+    "vh_str_fn": (_i32, [_vp, _i32, _vp, _u64, _vp, _i32, _vp, _i32, _i64, _i64, _i32, ctypes.c_char_p, _u64,
+                         ctypes.c_char_p, _u64, _vp, _u64, _vp, _u64, _vp, _i32, _vp]),
     "vh_strset_create": (_i32, [_i32, _u64, _p(_vp)]),
     "vh_strset_destroy": (_i32, [_vp]),
     "vh_strset_update": (_i32, [_vp, _vp, _i32, _vp, _u64]),

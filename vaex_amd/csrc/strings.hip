@@ -24,82 +24,23 @@
 // A string sits at level r only if every lower level holds a different string at its hash, so a
 // probe walks level 0, 1, ... and stops at the first level without its hash: absent.
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <atomic>
-#include <cstdlib>
 #include <deque>
 
 #include "common.hpp"
 #include "hashset.hpp"
 #include "slot_table.hpp"
-#include "str_dev.hpp"
+#include "str_col.hpp"
 
 namespace vh {
 
 constexpr uint64_t ROWFLAG = 1ULL << 62;  // payload: a row of the column being added (else a dictionary index)
 constexpr int STRSET_MAX_LEVELS = 64;
-constexpr int STR_MAX_PATTERN = 1024;
 
 static std::atomic<uint64_t> g_strset_rounds{0}, g_strset_form{0};
 uint64_t stat_strset_rounds(bool reset) { return reset ? g_strset_rounds.exchange(0) : g_strset_rounds.load(); }
 uint64_t stat_strset_form(bool reset) { return reset ? g_strset_form.exchange(0) : g_strset_form.load(); }
-
-struct StrCol {
-    const void *off;
-    const uint8_t *bytes;
-    int wide;  // int64 offsets
-};
-
-__device__ __forceinline__ int64_t col_off(const StrCol &c, uint64_t i) {
-    return c.wide ? static_cast<const int64_t *>(c.off)[i] : (int64_t) static_cast<const int32_t *>(c.off)[i];
-}
-__device__ __forceinline__ void row_range(const StrCol &c, uint64_t i, const uint8_t *&p, uint64_t &len) {
-    const int64_t a = col_off(c, i), e = col_off(c, i + 1);
-    p = c.bytes + a;
-    len = (uint64_t)(e - a);
-}
-
-static StrCol make_col(const void *off, int itemsize, const uint8_t *bytes) {
-    if (itemsize != 4 && itemsize != 8) fail(VH_ERR_ARG, "string offsets are int32 or int64");
-    return StrCol{off, bytes, itemsize == 8};
-}
-
-// the host's choice of form: wave per row from this mean length on (VH_STR_FORM=lane|wave pins it).
-// Measured: the lane form wins up to a mean of 128 bytes, the wave form from 256.
-constexpr uint64_t STR_WAVE_MEAN = 256;
-static bool wave_form(uint64_t total_bytes, uint64_t rows) {
-    const char *pin = std::getenv("VH_STR_FORM");  // read per call: scripts/str_bench.py flips it
-    if (pin && pin[0] == 'l') return false;
-    if (pin && pin[0] == 'w') return true;
-    return rows && total_bytes / rows >= STR_WAVE_MEAN;
-}
-// bytes the rows [0, n) of a checked column span (two offsets read back)
-static uint64_t col_span(const StrCol &c, uint64_t n) {
-    if (!n) return 0;
-    int64_t a = 0, e = 0;
-    const int isz = c.wide ? 8 : 4;
-    VH_HIP(hipMemcpyAsync(&a, c.off, isz, hipMemcpyDeviceToHost, stream()));
-    VH_HIP(hipMemcpyAsync(&e, static_cast<const char *>(c.off) + n * isz, isz, hipMemcpyDeviceToHost, stream()));
-    VH_HIP(hipStreamSynchronize(stream()));
-    if (!c.wide) {
-        int32_t a4, e4;
-        __builtin_memcpy(&a4, &a, 4);
-        __builtin_memcpy(&e4, &e, 4);
-        a = a4;
-        e = e4;
-    }
-    return e > a ? (uint64_t)(e - a) : 0;
-}
-
-// units (rows) of a launch: a lane or a wave each
-template <bool WAVE> __device__ __forceinline__ uint64_t unit_id() {
-    const uint64_t t = blockIdx.x * 256ull + threadIdx.x;
-    return WAVE ? t >> 6 : t;
-}
-template <bool WAVE> __device__ __forceinline__ uint64_t unit_stride() { return (uint64_t)gridDim.x * (WAVE ? 4 : 256); }
-template <bool WAVE> __device__ __forceinline__ bool unit_leader() { return !WAVE || (threadIdx.x & 63) == 0; }
-template <bool WAVE> static unsigned unit_blocks(uint64_t rows) { return blocks_for(WAVE ? rows * 64 : rows, 256, 16); }
 
 // p / len are the same in every lane of a wave in the wave forms
 template <bool WAVE> __device__ inline uint64_t row_hash(const uint8_t *p, uint64_t len, uint64_t seed, int bits) {
@@ -220,26 +161,17 @@ __global__ __launch_bounds__(256) void k_take_copy(StrCol c, uint64_t nsrc, cons
     }
 }
 
-struct TakeScratch {
-    DevBuf lens, tmp;
-};
+using TakeScratch = LenScratch;
+LenScratch &plan_scratch() {
+    thread_local LenScratch scratch;
+    return scratch;
+}
 // pos[0 .. m] = exclusive scan of the taken rows' lengths; returns the total
 template <typename I>
 static uint64_t take_plan(const StrCol &c, uint64_t nsrc, const I *idx, uint64_t m, uint64_t *pos, TakeScratch &s) {
-    hipStream_t st = stream();
-    s.lens.ensure((m + 1) * 8);
-    hipLaunchKernelGGL(k_take_len<I>, dim3(blocks_for(m + 1, 256)), dim3(256), 0, st, c, nsrc, idx, m, s.lens.as<uint64_t>());
+    hipLaunchKernelGGL(k_take_len<I>, dim3(blocks_for(m + 1, 256)), dim3(256), 0, stream(), c, nsrc, idx, m, s.lengths(m));
     VH_HIP(hipGetLastError());
-    size_t tb = 0;
-    VH_HIP(rocprim::exclusive_scan(nullptr, tb, s.lens.as<uint64_t>(), pos, (uint64_t)0, (size_t)(m + 1),
-                                   rocprim::plus<uint64_t>(), st));
-    s.tmp.ensure(tb ? tb : 8);
-    VH_HIP(rocprim::exclusive_scan(s.tmp.ptr, tb, s.lens.as<uint64_t>(), pos, (uint64_t)0, (size_t)(m + 1),
-                                   rocprim::plus<uint64_t>(), st));
-    uint64_t total = 0;
-    VH_HIP(hipMemcpyAsync(&total, pos + m, 8, hipMemcpyDeviceToHost, st));
-    VH_HIP(hipStreamSynchronize(st));
-    return total;
+    return scan_lengths(s, m, pos);
 }
 template <typename I>
 static void take_copy(const StrCol &c, uint64_t nsrc, const I *idx, uint64_t m, const uint64_t *pos, uint64_t total,
@@ -563,7 +495,7 @@ int vh_str_take_plan(const void *offsets, int off_itemsize, uint64_t n, const vo
                      uint64_t *pos, uint64_t *total) {
     VH_API_BEGIN
     const StrCol c = make_col(offsets, off_itemsize, nullptr);
-    thread_local TakeScratch scratch;
+    TakeScratch &scratch = plan_scratch();
     if (idx_itemsize == 8) *total = take_plan(c, n, static_cast<const int64_t *>(indices), m, pos, scratch);
     else if (idx_itemsize == 4) *total = take_plan(c, n, static_cast<const int32_t *>(indices), m, pos, scratch);
     else fail(VH_ERR_ARG, "vh_str_take_plan: indices are int32 or int64");

@@ -252,6 +252,31 @@ class StringOperations:
             raise NotImplementedError("str.contains: regular expressions are not supported (regex=False)")
         return self._call("str_contains", pat)
 
+    # the string-producing functions (strings.TRANSFORMS; csrc/strfn.hip): each gives a string
+    # expression again, so they chain (df.s.str.strip().str.lower().str.startswith('id'))
+    def lower(self): return self._call("str_lower")
+    def upper(self, ascii=False): return self._call("str_upper", ascii) if ascii else self._call("str_upper")
+    def slice(self, start=0, stop=None): return self._call("str_slice", start, stop)
+    def strip(self, to_strip=None): return self._call("str_strip", to_strip)
+    def lstrip(self, to_strip=None): return self._call("str_lstrip", to_strip)
+    def rstrip(self, to_strip=None): return self._call("str_rstrip", to_strip)
+    def pad(self, width, side="left", fillchar=" "): return self._call("str_pad", width, side, fillchar)
+    def ljust(self, width, fillchar=" "): return self._call("str_ljust", width, fillchar)
+    def rjust(self, width, fillchar=" "): return self._call("str_rjust", width, fillchar)
+    def center(self, width, fillchar=" "): return self._call("str_center", width, fillchar)
+    def zfill(self, width): return self._call("str_zfill", width)
+    def repeat(self, repeats): return self._call("str_repeat", repeats)
+
+    def cat(self, other):
+        e = self.expression
+        o = other.expression if isinstance(other, Expression) else repr(other)
+        return Expression(e.df, f"str_cat({e.expression}, {o})")
+
+    def replace(self, pat, repl, n=-1, flags=0, regex=False):
+        if regex or flags:
+            raise NotImplementedError("str.replace: regular expressions are not supported (regex=False, flags=0)")
+        return self._call("str_replace", pat, repl, n)
+
 
 def _ordinal_values(x, ordered_set):
     """functions.py:2441-2448 (host evaluation; the bin kernel fuses it instead)."""
@@ -308,8 +333,45 @@ class DataFrame:
         return any(isinstance(c, (DeviceArray, DeviceStringArray)) for c in self.columns.values())
 
     def _is_string(self, expression):
-        """Whether the expression names a string column (strings.DeviceStringArray)."""
-        return isinstance(self.columns.get(str(expression)), DeviceStringArray)
+        """Whether the expression is string-valued: a string column (strings.DeviceStringArray),
+        or a transform of one / a virtual column of that kind (expr.py ``_string_source``)."""
+        expression = str(expression)
+        if expression in self.columns:
+            return isinstance(self.columns[expression], DeviceStringArray)
+        return self._string_plan(expression) is not None
+
+    def _string_plan(self, expression):
+        """The plan of a string-valued expression (expr.string_plan), None for any other; a
+        frame without string columns has none.  Plans are kept per expression text while the
+        frame's structure (which columns are strings, the virtual columns) stays the same, so
+        evaluate / data_type / _is_string parse and check an expression once."""
+        structure = tuple((k, isinstance(c, DeviceStringArray)) for k, c in self.columns.items())
+        if not any(is_string for _, is_string in structure):
+            return None
+        expression = str(expression)
+        key = (structure, tuple(sorted(self.virtual_columns.items())))
+        cache = self.__dict__.setdefault("_string_plans", [None, {}])
+        if cache[0] != key:
+            cache[:] = [key, {}]
+        if expression in cache[1]:
+            return cache[1][expression]
+        from .expr import UnsupportedExpression, string_plan
+        try:
+            plan = string_plan(self, expression)
+        except UnsupportedExpression as e:
+            raise NotImplementedError(f"expression {expression!r} over HBM columns: {e}") from None
+        if len(cache[1]) > 256:
+            cache[1].clear()
+        cache[1][expression] = plan
+        return plan
+
+    @staticmethod
+    def _hidden_name(name):
+        """the hidden codes column of the string key ``name`` (a column name or an expression)"""
+        if name.isidentifier():
+            return f"__str_{name}"
+        import hashlib
+        return "__str_expr_" + hashlib.sha1(name.encode("utf-8", "surrogatepass")).hexdigest()[:16]
 
     def get_column_names(self):
         return list(self.columns) + list(self.virtual_columns)
@@ -413,6 +475,10 @@ class DataFrame:
             block = col[i1:i2]
             return block[filter_mask] if filter_mask is not None else block
         if self.is_device_resident():
+            plan = self._string_plan(expression)
+            if plan is not None:  # string-valued: a temporary DeviceStringArray of the rows
+                from .expr import evaluate_string
+                return evaluate_string(self, plan, i1, i2)
             return self._eval_device(expression, i1, i2)
         if expression in self.virtual_columns:
             return self._eval_host(self.virtual_columns[expression], i1, i2, filter_mask)
@@ -1264,23 +1330,27 @@ class DataFrame:
 
     # ---- string keys ---------------------------------------------------------------
     def _encoded(self, names):
-        """(frame, {hidden column: dictionary keys}): a copy in which each string column in
-        ``names`` has a hidden int32 column of its first-appearance codes beside it (the
-        dictionary encoder, strings.encode), named ``__str_<name>``.  Codes are kept per live
-        column object."""
+        """(frame, {hidden column: dictionary keys}): a copy in which each string key in
+        ``names`` (a string column or a string-valued expression) has a hidden int32 column of
+        its first-appearance codes beside it (the dictionary encoder, strings.encode), named
+        ``_hidden_name(name)``.  An expression is materialised over the frame once, encoded and
+        dropped.  Codes are kept per key text while its plan (which spells out the virtual
+        columns it goes through) is the same and its source columns are the same live objects."""
+        from .expr import evaluate_string, plan_columns
         from .strings import encode
         df = self.copy()
         cache = self.__dict__.setdefault("_string_codes", {})
         keys = {}
         for name in names:
-            col = self.columns[name]
+            plan = ("col", name) if name in self.columns else self._string_plan(name)
+            sources = [self.columns[n] for n in plan_columns(plan)]
             hit = cache.get(name)
-            if hit is None or hit[0] is not col:
-                codes, sset = encode(col)
-                hit = cache[name] = (col, codes, sset.key_array())
-            hidden = f"__str_{name}"
-            df.columns[hidden] = hit[1]
-            keys[hidden] = hit[2]
+            if hit is None or hit[0] != plan or len(hit[1]) != len(sources) or any(a is not b for a, b in zip(hit[1], sources)):
+                codes, sset = encode(evaluate_string(self, plan, 0, self._length))
+                hit = cache[name] = (plan, sources, codes, sset.key_array())
+            hidden = self._hidden_name(name)
+            df.columns[hidden] = hit[2]
+            keys[hidden] = hit[3]
         return df, keys
 
     def _string_value_counts(self, expression, ascending, selection):

@@ -180,16 +180,97 @@ class Compiler:
             return node.id
         return None
 
-    def _string_input(self, fn, name, arg=None):
-        """A string function of a string column (``str_*``, strings.py) as one more input column
-        of the program: the string kernel fills it for the rows [i1, i2) at evaluate time
+    def _string_source(self, node, depth=0):
+        """The plan of a string-valued ast node, else None.  String-valued: a string column's
+        name, a virtual column whose expression is string-valued, a transform call
+        (``strings.TRANSFORMS``) whose first argument is string-valued, and ``+`` with a
+        string-valued side (``str_cat``).  A plan is ``("col", name)`` or ``("fn", method, plan,
+        args, kwargs)`` for a ``DeviceStringArray`` method, hashable; :func:`evaluate_string`
+        computes it for a row range."""
+        from . import strings
+        if depth > 32:
+            raise UnsupportedExpression("string expression too deeply nested")
+        if isinstance(node, ast.Expression):
+            return self._string_source(node.body, depth)
+        if isinstance(node, ast.Name):
+            if self._string_column(node):
+                return ("col", node.id)
+            if node.id not in self.df.columns and node.id in self.df.virtual_columns:
+                try:
+                    tree = ast.parse(self.df.virtual_columns[node.id], mode="eval")
+                except SyntaxError as e:
+                    raise UnsupportedExpression(str(e))
+                return self._string_source(tree, depth + 1)
+            return None
+        if isinstance(node, ast.BinOp) and isinstance(node.op, ast.Add):
+            a, b = node.left, node.right
+            lit_a = isinstance(a, ast.Constant) and isinstance(a.value, str)
+            lit_b = isinstance(b, ast.Constant) and isinstance(b.value, str)
+            sa = None if lit_a else self._string_source(a, depth + 1)
+            sb = None if lit_b else self._string_source(b, depth + 1)
+            if sa is None and sb is None:
+                return None
+            if sa is not None and sb is not None:
+                return self._transform_plan("cat", sa, (("plan", sb),), {})
+            if sa is not None and lit_b:
+                return self._transform_plan("cat", sa, (b.value,), {})
+            if sb is not None and lit_a:
+                return self._transform_plan("cat", sb, (a.value,), {"first": True})
+            raise UnsupportedExpression("+ of a string expression takes a str constant or a string expression")
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in strings.TRANSFORMS:
+            name = node.func.id
+            args = list(node.args)
+            kwargs = {}
+            if name == "str_cat" and len(args) == 2 and isinstance(args[0], ast.Constant) and isinstance(args[0].value, str):
+                args = [args[1], args[0]]  # the reference's form of 'lit' + s: str_cat('lit', s)
+                kwargs["first"] = True
+            src = self._string_source(args[0], depth + 1) if args else None
+            if src is None:
+                raise UnsupportedExpression(f"{name} takes a string column or a string-valued expression")
+            values = []
+            for a in args[1:]:
+                other = self._string_source(a, depth + 1) if name == "str_cat" and not isinstance(a, ast.Constant) else None
+                values.append(("plan", other) if other is not None else self._literal(name, a))
+            for k in node.keywords:
+                if k.arg is None or k.arg == "first":
+                    raise UnsupportedExpression(f"{name}: keyword arguments by name")
+                kwargs[k.arg] = self._literal(name, k.value)
+            return self._transform_plan(strings.TRANSFORMS[name], src, tuple(values), kwargs, name)
+        return None
+
+    @staticmethod
+    def _literal(name, node):
+        try:
+            v = ast.literal_eval(node)
+        except (ValueError, TypeError, SyntaxError):
+            raise UnsupportedExpression(f"{name}: arguments after the first are constants")
+        if v is not None and not isinstance(v, (str, int, bool)):
+            raise UnsupportedExpression(f"{name}: argument {v!r}")
+        return v
+
+    @staticmethod
+    def _transform_plan(method, src, args, kwargs, name=None):
+        """the plan of ``src.method(*args, **kwargs)``, the arguments checked now: a wrong
+        signature is UnsupportedExpression; what the method itself refuses (a regular expression,
+        a fill of two characters ...) raises its NotImplementedError / ValueError here"""
+        from . import strings
+        dry = [strings.COLUMN if isinstance(a, tuple) else a for a in args]
+        try:
+            strings.transform_arguments(method, *dry, **kwargs)
+        except TypeError as e:
+            raise UnsupportedExpression(f"{name or method}: {e}")
+        return ("fn", method, src, args, tuple(sorted(kwargs.items())))
+
+    def _string_input(self, fn, source, arg=None):
+        """A string function of a string-valued source (``str_*``, strings.py) as one more input
+        column of the program: the string kernel fills it for the rows [i1, i2) at evaluate time
         (Program.evaluate), a bool mask for the predicates, int64 for the lengths."""
         from . import strings
         if fn in strings.MATCH_OPS:
             if not isinstance(arg, str):
                 raise UnsupportedExpression(f"{fn}: the pattern is a str constant")
             strings._pattern(arg)  # NotImplementedError past 1024 bytes
-        key = ("str", fn, name, arg)
+        key = ("str", fn, source, arg)
         if key not in self.columns:
             if len(self.columns) >= MAX_COLS:
                 raise UnsupportedExpression("too many columns")
@@ -491,13 +572,14 @@ class Compiler:
 
     def v_Compare(self, node):
         if len(node.ops) == 1 and isinstance(node.ops[0], (ast.Eq, ast.NotEq)):
-            # string column == / != 'constant' (either side): str_equals / str_notequals
+            # string expression == / != 'constant' (either side): str_equals / str_notequals
             a, b = node.left, node.comparators[0]
             for col, con in ((a, b), (b, a)):
-                name = self._string_column(col)
-                if name and isinstance(con, ast.Constant) and isinstance(con.value, str):
-                    return self._string_input("str_equals" if isinstance(node.ops[0], ast.Eq) else "str_notequals",
-                                              name, con.value)
+                if isinstance(con, ast.Constant) and isinstance(con.value, str) and not isinstance(col, ast.Constant):
+                    source = self._string_source(col)
+                    if source is not None:
+                        return self._string_input("str_equals" if isinstance(node.ops[0], ast.Eq) else "str_notequals",
+                                                  source, con.value)
         left = self.visit(node.left)
         out = None
         for op, comp in zip(node.ops, node.comparators):
@@ -528,6 +610,10 @@ class Compiler:
         from . import strings
         if name in strings.FUNCTIONS:
             return self._string_call(name, node)
+        if name in strings.TRANSFORMS:
+            self._string_source(node)  # its own refusals first
+            raise UnsupportedExpression(f"{name} gives strings: a program computes numbers (its str_* predicates and "
+                                        "lengths take it as their argument)")
         if node.keywords:
             raise UnsupportedExpression("keyword arguments")
         if name == "astype" and len(node.args) == 2:
@@ -614,9 +700,10 @@ class Compiler:
 
     def _string_call(self, name, node):
         """``str_len(s)`` / ``str_byte_length(s)`` / ``str_<predicate>(s, 'literal')`` over a string
-        column (``str_contains`` also with ``regex=False`` or a third positional False)."""
+        column or a string-valued expression (``str_contains`` also with ``regex=False`` or a third
+        positional False)."""
         from . import strings
-        col = self._string_column(node.args[0]) if node.args else None
+        col = self._string_source(node.args[0]) if node.args else None
         if col is None:
             raise UnsupportedExpression(f"{name} takes a string column")
         rest = list(node.args[1:])
@@ -752,10 +839,11 @@ class Program:
         n = i2 - i1
         cols = []
         keep = []
+        strings = {}  # the transformed sources of this evaluation, each computed once
         for name in self.columns:
             if isinstance(name, tuple):  # a string function's column (Compiler._string_input)
-                _, fn, cname, arg = name
-                scol = df.columns[cname][i1:i2]
+                _, fn, source, arg = name
+                scol = evaluate_string(df, source, i1, i2, strings)
                 cols.append(scol.match(fn, arg) if arg is not None else scol.len(fn))
                 continue
             col = df.columns[name]
@@ -777,6 +865,45 @@ class Program:
         if keep:
             _lib.synchronize()  # the staged columns are freed on return
         return out
+
+
+def string_plan(df, expression):
+    """The plan of a string-valued expression on ``df`` (``Compiler._string_source``), None for
+    any other expression."""
+    try:
+        tree = ast.parse(str(expression), mode="eval")
+    except SyntaxError:
+        return None
+    return Compiler(df)._string_source(tree)
+
+
+def plan_columns(plan):
+    """the names of the string columns a plan reads, in order, each once"""
+    if plan[0] == "col":
+        return [plan[1]]
+    names = plan_columns(plan[2])
+    for a in plan[3]:
+        if isinstance(a, tuple):
+            names += [n for n in plan_columns(a[1]) if n not in names]
+    return names
+
+
+def evaluate_string(df, plan, i1, i2, memo=None):
+    """The DeviceStringArray of a plan for the rows [i1, i2): transforms are row-local, so the
+    source columns are sliced (views) and every transform runs over the slice.  ``memo`` (plan ->
+    column, for one row range) lets the plans of one evaluation share what they have in common:
+    ``str_lower(s)`` runs once under two predicates."""
+    if plan[0] == "col":
+        return df.columns[plan[1]][i1:i2]
+    if memo is not None and plan in memo:
+        return memo[plan]
+    _, method, src, args, kwargs = plan
+    col = evaluate_string(df, src, i1, i2, memo)
+    args = [evaluate_string(df, a[1], i1, i2, memo) if isinstance(a, tuple) else a for a in args]
+    out = getattr(col, method)(*args, **dict(kwargs))
+    if memo is not None:
+        memo[plan] = out
+    return out
 
 
 _CACHE = {}

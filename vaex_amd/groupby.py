@@ -688,19 +688,20 @@ def groupby_string_keys(df, bys, multikey, agg, sort=False, assume_sparse="auto"
     edf, keys = df._encoded(names)
     tables = {}
     for name in names:
-        hidden = f"__str_{name}"
+        hidden = df._hidden_name(name)
         table = keys[hidden]
         if sort:
             edf.columns[hidden], order = rank_codes(edf.columns[hidden], table)
             table = table[np.asarray(order, dtype=np.int64)]
         tables[hidden] = table
-    hidden_by = [f"__str_{b}" if b in names else b for b in bys]
+    hidden_by = [df._hidden_name(b) if b in names else b for b in bys]
+    shown = {df._hidden_name(b): b for b in names}  # a key's result column carries the key's own text
     res = edf.groupby(hidden_by if multikey else hidden_by[0], agg=agg, sort=sort, assume_sparse=assume_sparse,
                       row_limit=row_limit)
     columns = {}
     for k, v in res.columns.items():
         if k in tables:
-            columns[k[len("__str_"):]] = tables[k][np.asarray(v).astype(np.int64)]
+            columns[shown[k]] = tables[k][np.asarray(v).astype(np.int64)]
         else:
             columns[k] = v
     return DataFrame(columns)

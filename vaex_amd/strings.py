@@ -24,6 +24,17 @@ MAX_PATTERN = 1024    # bytes of a literal pattern (strings.hip stages it in LDS
 MATCH_OPS = {"str_equals": 0, "str_notequals": 1, "str_startswith": 2, "str_endswith": 3, "str_contains": 4}
 LEN_KINDS = {"str_byte_length": 0, "str_len": 1}
 FUNCTIONS = tuple(MATCH_OPS) + tuple(LEN_KINDS)
+# the string-producing functions (functions.py ``str_*``) -> the DeviceStringArray method that
+# computes them; each takes the reference's arguments after the column
+TRANSFORMS = {"str_lower": "lower", "str_upper": "upper", "str_slice": "slice", "str_strip": "strip",
+              "str_lstrip": "lstrip", "str_rstrip": "rstrip", "str_pad": "pad", "str_ljust": "ljust",
+              "str_rjust": "rjust", "str_center": "center", "str_zfill": "zfill", "str_repeat": "repeat",
+              "str_cat": "cat", "str_replace": "replace"}
+TRANSFORM_OPS = {"lower": 0, "upper": 1, "slice": 2, "strip": 3, "pad": 4, "repeat": 5, "cat": 6, "replace": 7}  # str_dev.hpp
+SIDES = {"left": 1, "right": 2, "both": 3}
+WHITESPACE = " \t\n\v\f\r"   # C isspace: what strip() without an argument strips (string_utils.hpp:265-306)
+TOO_LONG = 2 ** 64 - 1          # vh_str_fn_plan's total when the result cannot fit (VH_STR_FN_TOO_LONG)
+MAX_CASE_TABLE = 2048          # pairs of a case table (strfn.hip stages it in LDS)
 
 
 class _StringType:
@@ -53,6 +64,60 @@ def take_offset_dtype(input_dtype, total_bytes):
     if np.dtype(input_dtype) == np.int64 or total_bytes >= 2 ** 31:
         return np.dtype(np.int64)
     return np.dtype(np.int32)
+
+
+# ---- the case tables ------------------------------------------------------------------------------
+def case_mapping(upper):
+    """{code point: image} over the code points >= 128 that lower (``upper`` False) or upper
+    changes, one code point to one code point: ``pyarrow.compute.utf8_lower`` / ``utf8_upper``,
+    which is what the reference calls (functions.py:1528-1558, 2102-2138).  Without pyarrow:
+    Python's ``str.lower`` / ``str.upper`` where the result is one code point, the identity
+    elsewhere.  ASCII is mapped inline by the kernel."""
+    cps = np.concatenate([np.arange(0x80, 0xD800, dtype=np.uint32), np.arange(0xE000, 0x110000, dtype=np.uint32)])
+    try:
+        import pyarrow as pa
+        import pyarrow.compute as pc
+    except ImportError:
+        out = {}
+        for cp in cps.tolist():
+            t = chr(cp).upper() if upper else chr(cp).lower()
+            if len(t) == 1 and ord(t) != cp:
+                out[cp] = ord(t)
+        return out
+    ar = pa.array(cps.view("<U1"), type=pa.string())
+    images = (pc.utf8_upper if upper else pc.utf8_lower)(ar)
+    changed = pc.and_(pc.equal(pc.utf8_length(images), 1), pc.not_equal(images, ar)).to_numpy(zero_copy_only=False)
+    rows = np.flatnonzero(changed)
+    return {int(cps[i]): ord(t) for i, t in zip(rows.tolist(), images.take(pa.array(rows)).to_pylist())}
+
+
+def pack_case_table(mapping):
+    """The kernel's layout of a mapping: a uint32 array of (code point, image) pairs sorted by
+    code point (a binary search in LDS, str_dev.hpp ``case_image``)."""
+    if any(k < 0x80 for k in mapping):
+        raise ValueError("a case table holds code points from 128 on")
+    if len(mapping) > MAX_CASE_TABLE:
+        raise NotImplementedError(f"a case table of {len(mapping)} pairs: the device kernel takes at most {MAX_CASE_TABLE}")
+    out = np.empty((len(mapping), 2), np.uint32)
+    for i, k in enumerate(sorted(mapping)):
+        out[i] = k, mapping[k]
+    return out.reshape(-1)
+
+
+def unpack_case_table(table):
+    pairs = np.asarray(table, np.uint32).reshape(-1, 2)
+    return {int(k): int(v) for k, v in pairs}
+
+
+_case_tables = {}
+
+
+def case_table(upper):
+    """The packed table of :func:`case_mapping`, built once per process."""
+    t = _case_tables.get(bool(upper))
+    if t is None:
+        t = _case_tables[bool(upper)] = pack_case_table(case_mapping(upper))
+    return t
 
 
 def _bytes_buffer(data):
@@ -243,6 +308,93 @@ class DeviceStringArray:
         _lib.call("vh_str_match", optr, oisz, bptr, self.length, MATCH_OPS[op], pat, len(pat), out.ptr)
         return out
 
+    # ---- transforms: a new column each (csrc/strfn.hip) ---------------------------
+    def _transform(self, op, a=0, b=0, flags=0, c0=b"", c1=b"", table=None, other=None):
+        """The plan (every row's result length, scanned into positions on the device) and the
+        write, with the output sized in between, like :meth:`take`."""
+        n = self.length
+        pos = DeviceArray(n + 1, np.uint64)
+        total = ctypes.c_uint64(0)
+        second = other._args() if other is not None else (None, 0, None)
+        tptr, nt = (table.ctypes.data, len(table) // 2) if table is not None and len(table) else (None, 0)
+        optr, oisz, bptr = self._args()
+        args = (optr, oisz, bptr, n) + second + (TRANSFORM_OPS[op], int(a), int(b), int(flags), c0, len(c0), c1, len(c1),
+                                                 tptr, nt)
+        _lib.call("vh_str_fn_plan", *args, pos.ptr, ctypes.byref(total))
+        if total.value == TOO_LONG:
+            # repeats and widths are any int64: the device found a row, or the sum, past what
+            # offsets can address, and nothing is allocated or written
+            raise MemoryError(f"str {op}: the result's bytes do not fit (a row past 2^62 / rows)")
+        widths = [self.offsets.dtype] + ([other.offsets.dtype] if other is not None else [])
+        odt = take_offset_dtype(max(widths, key=lambda dt: np.dtype(dt).itemsize), total.value)
+        out_off = DeviceArray(n + 1, odt)
+        try:
+            full = DeviceArray(total.value + SLACK, np.uint8)
+        except _lib.HipError as e:
+            raise MemoryError(f"str {op}: a result of {total.value} bytes: {e}") from None
+        _lib.call("vh_str_fn", *args, pos.ptr, total.value, out_off.ptr, odt.itemsize, full.ptr)
+        return DeviceStringArray(out_off, full, _checked=True, _root=(full, total.value))
+
+    def lower(self):
+        """``str_lower``: one code point to one code point (``pyarrow.compute.utf8_lower``)."""
+        return self._transform(**transform_arguments("lower"))
+
+    def upper(self, ascii=False):
+        """``str_upper``; ``ascii=True`` maps only a-z."""
+        return self._transform(**transform_arguments("upper", ascii))
+
+    def slice(self, start=0, stop=None):
+        """``str_slice``: ``s[start:stop]`` counted in code points, negative bounds as Python's."""
+        return self._transform(**transform_arguments("slice", start, stop))
+
+    def strip(self, to_strip=None):
+        """``str_strip``: without an argument the six bytes of C ``isspace`` (not Unicode white
+        space); with one, a set of ASCII characters; ``''`` strips nothing."""
+        return self._transform(**transform_arguments("strip", to_strip))
+
+    def lstrip(self, to_strip=None):
+        return self._transform(**transform_arguments("lstrip", to_strip))
+
+    def rstrip(self, to_strip=None):
+        return self._transform(**transform_arguments("rstrip", to_strip))
+
+    def pad(self, width, side="left", fillchar=" "):
+        """``str_pad``: to ``width`` code points with one ASCII ``fillchar`` on ``side`` ('left',
+        'right', 'both': CPython's ``center`` split)."""
+        return self._transform(**transform_arguments("pad", width, side, fillchar))
+
+    def ljust(self, width, fillchar=" "):
+        return self._transform(**transform_arguments("ljust", width, fillchar))
+
+    def rjust(self, width, fillchar=" "):
+        return self._transform(**transform_arguments("rjust", width, fillchar))
+
+    def center(self, width, fillchar=" "):
+        return self._transform(**transform_arguments("center", width, fillchar))
+
+    def zfill(self, width):
+        """``str_zfill``: left padding with '0' and nothing more ('-5' at 4 is '00-5')."""
+        return self._transform(**transform_arguments("zfill", width))
+
+    def repeat(self, repeats):
+        """``str_repeat``; ``repeats <= 0`` gives empty strings."""
+        return self._transform(**transform_arguments("repeat", repeats))
+
+    def cat(self, other, first=False):
+        """``str_cat``: ``self + other`` for a str constant or a second column of the same
+        length; ``first=True`` puts a constant before the rows (``'lit' + s``)."""
+        kw = transform_arguments("cat", other, first)
+        if kw.get("other") is not None:
+            if other.length != self.length:
+                raise ValueError(f"cat of columns of {self.length} and {other.length} rows")
+            if first:
+                return other.cat(self)
+        return self._transform(**kw)
+
+    def replace(self, pat, repl, n=-1, flags=0, regex=False):
+        """``str_replace``: literal, leftmost, non-overlapping; ``n < 0``: every occurrence."""
+        return self._transform(**transform_arguments("replace", pat, repl, n, flags, regex))
+
 
 def _pattern(pattern):
     if not isinstance(pattern, str):
@@ -251,6 +403,98 @@ def _pattern(pattern):
     if len(pat) > MAX_PATTERN:
         raise NotImplementedError(f"a pattern of {len(pat)} bytes: the device kernel takes at most {MAX_PATTERN}")
     return pat
+
+
+# ---- the transforms' arguments ---------------------------------------------------------------------
+# One checker per method of TRANSFORMS, with the method's signature after the column: it raises
+# what the method refuses and returns the keywords of DeviceStringArray._transform.  The methods
+# call them, and so does expr.py when it compiles a transform call (with COLUMN where an argument
+# is another string expression), so an expression is refused when it is made, with the method's
+# own error.
+COLUMN = object()
+
+
+def _pad_arguments(width, side="left", fillchar=" "):
+    if side not in SIDES:
+        raise ValueError(f"side is 'left', 'right' or 'both', not {side!r}")
+    return dict(op="pad", a=_int(width, "width"), flags=SIDES[side], c0=_fillchar(fillchar))
+
+
+def _strip_arguments(side, to_strip=None):
+    return dict(op="strip", flags=SIDES[side], c0=_strip_set(to_strip))
+
+
+def _slice_arguments(start=0, stop=None):
+    start = 0 if start is None else _int(start, "start")
+    if stop is None:
+        return dict(op="slice", a=start)
+    return dict(op="slice", a=start, b=_int(stop, "stop"), flags=1)
+
+
+def _cat_arguments(other, first=False):
+    if other is COLUMN or isinstance(other, DeviceStringArray):
+        return dict(op="cat", flags=2, other=other)
+    return dict(op="cat", flags=1 if first else 0, c0=_pattern(other))
+
+
+def _replace_arguments(pat, repl, n=-1, flags=0, regex=False):
+    if regex or flags:
+        raise NotImplementedError("str_replace: regular expressions are not supported (regex=False, flags=0)")
+    pat, repl = _pattern(pat), _pattern(repl)
+    if not pat:
+        raise ValueError("str_replace: the pattern is not empty")
+    return dict(op="replace", a=_int(n, "n"), c0=pat, c1=repl)
+
+
+_ARGUMENTS = {
+    "lower": lambda: dict(op="lower", table=case_table(False)),
+    "upper": lambda ascii=False: dict(op="upper", flags=1) if ascii else dict(op="upper", table=case_table(True)),
+    "slice": _slice_arguments,
+    "strip": lambda to_strip=None: _strip_arguments("both", to_strip),
+    "lstrip": lambda to_strip=None: _strip_arguments("left", to_strip),
+    "rstrip": lambda to_strip=None: _strip_arguments("right", to_strip),
+    "pad": _pad_arguments,
+    "ljust": lambda width, fillchar=" ": _pad_arguments(width, "right", fillchar),
+    "rjust": lambda width, fillchar=" ": _pad_arguments(width, "left", fillchar),
+    "center": lambda width, fillchar=" ": _pad_arguments(width, "both", fillchar),
+    "zfill": lambda width: _pad_arguments(width, "left", "0"),
+    "repeat": lambda repeats: dict(op="repeat", a=_int(repeats, "repeats")),
+    "cat": _cat_arguments,
+    "replace": _replace_arguments,
+}
+
+
+def transform_arguments(method, *args, **kwargs):
+    """The ``_transform`` keywords of ``column.method(*args, **kwargs)``, the arguments checked."""
+    return _ARGUMENTS[method](*args, **kwargs)
+
+
+def _int(value, what):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"{what} is an integer, not {value!r}")
+    if not -(1 << 63) <= int(value) < (1 << 63):
+        raise ValueError(f"{what} out of the int64 range")
+    return int(value)
+
+
+def _strip_set(to_strip):
+    """the bytes strip removes: ASCII only (the reference strips bytes, which would cut a code
+    point of more than one byte in half)"""
+    if to_strip is None:
+        to_strip = WHITESPACE
+    chars = _pattern(to_strip)
+    if any(c >= 0x80 for c in chars):
+        raise NotImplementedError("strip: to_strip holds ASCII characters only")
+    return chars
+
+
+def _fillchar(fillchar):
+    if not isinstance(fillchar, str):
+        raise TypeError("fillchar is a str")
+    fill = fillchar.encode("utf-8", "surrogatepass")
+    if len(fill) != 1 or fill[0] >= 0x80:
+        raise ValueError("fillchar is exactly one ASCII character")
+    return fill
 
 
 class ordered_set_string:
