@@ -417,7 +417,12 @@ int vh_hashagg_exchange(vh_hashagg *h, vh_comm *comm, int gather);
  * out[i] = program(cols[.][i]) for i < n: the device evaluation of a virtual column,
  * selection or filter (the reference evaluates them with numpy per chunk, cpu.py:542-581,
  * execution.py:337-341).  code: stack program compiled by vaex_amd/expr.py (op | arg << 8),
- * consts: 64-bit constant bit patterns; HBM columns and output. */
+ * consts: 64-bit constant bit patterns; HBM columns and output.  Three program shapes run a
+ * kernel of their own, 8 rows per lane, with results identical to the interpreter's: a
+ * conjunction / disjunction of column-constant comparisons (VH_EXPR_TERMS=0 turns it off),
+ * COL DT_FIELD (VH_EXPR_DTFIELD=0), and COL(1-byte mask) CONST COL(data) WHERE with 4- or 8-byte
+ * items and the data column's dtype as the result's: fillmissing(column, constant)
+ * (VH_EXPR_FILL=0); each switch is read per call. */
 int vh_expr_eval(const uint32_t *code, int ncode, const uint64_t *consts, int nconsts, const void *const *cols,
                  const int *col_dtypes, int ncols, uint64_t n, int out_dtype, void *out);
 
@@ -444,6 +449,21 @@ int vh_pnpoly(const void *x, int x_dtype, const void *y, int y_dtype, uint64_t n
 /* out = mode(a == 1, b == 1) as 0 / 1 bytes; b NULL: out = !(a == 1).  HBM buffers; out may be
  * a or b.  Only bytes equal to 1 count as selected, as everywhere in the engine. */
 int vh_mask_combine(const uint8_t *a, const uint8_t *b, int mode, uint64_t n, uint8_t *out);
+
+/* ---- missing-value masks of HBM columns (missing.hip) ---------------------------
+ * A missing mask is one uint8 per row, 1 = missing (numpy's convention, the one
+ * vh_binner_set_data_mask / vh_agg_set_data_mask take).  Every buffer is in HBM.
+ * vh_mask_unpack_bits: an Arrow validity bitmap (bit i of byte i / 8, LSB first, 1 = valid) to a
+ * byte mask: out[i] = !bit(bit_offset + i) for i < n.  bits holds (bit_offset + n + 7) / 8 bytes;
+ * nothing past them is read.  One lane per 8 rows, one 8-byte store (byte stores for a ragged
+ * tail or a destination that is not 8-aligned).
+ * vh_mask_pack_bits: the reverse at bit offset 0: bit i of out_bits = (mask[i] == 0), the padding
+ * bits of the last of its (n + 7) / 8 bytes 0.  Any non-zero mask byte is missing.
+ * vh_mask_count: *count = the number of non-zero bytes of mask[0 .. n) (synchronises).
+ * VH_ERR_ARG: a null or host buffer with n > 0. */
+int vh_mask_unpack_bits(const uint8_t *bits, uint64_t bit_offset, uint64_t n, uint8_t *out);
+int vh_mask_pack_bits(const uint8_t *mask, uint64_t n, uint8_t *out_bits);
+int vh_mask_count(const uint8_t *mask, uint64_t n, uint64_t *count);
 
 /* combined int64 key of a multi-key groupby, out[i] = sum_j (cols[j][i] - mins[j]) * mults[j]
  * (the cartesian ordinal of groupby.py:248-288 _combine, first key most significant);

@@ -19,7 +19,7 @@ reference's plugin surface for that path:
 from . import _lib  # noqa: F401  (fails loudly if the HIP library is missing)
 from . import agg, superagg, superutils  # noqa: F401
 from .dataframe import DataFrame, Expression, RowLimitException, from_arrays, from_dict  # noqa: F401
-from .device import DeviceArray  # noqa: F401
+from .device import DeviceArray, DeviceMaskedArray  # noqa: F401
 from .execution import ExecutorLocal, default_executor  # noqa: F401
 from .groupby import BinnerTime  # noqa: F401
 from .strings import DeviceStringArray  # noqa: F401

@@ -134,6 +134,9 @@ SIGNATURES = {
     "vh_mask_rows": (_i32, [_vp, _u64, _i32, _vp, _p(_u64)]),
     "vh_pnpoly": (_i32, [_vp, _i32, _vp, _i32, _u64, _p(_dbl), _p(_dbl), _i32, _dbl, _dbl, _dbl, _vp, _i32, _vp]),
     "vh_mask_combine": (_i32, [_vp, _vp, _i32, _u64, _vp]),
+    "vh_mask_unpack_bits": (_i32, [_vp, _u64, _u64, _vp]),
+    "vh_mask_pack_bits": (_i32, [_vp, _u64, _vp]),
+    "vh_mask_count": (_i32, [_vp, _u64, _p(_u64)]),
     "vh_expr_eval": (_i32, [_p(ctypes.c_uint32), _i32, _p(_u64), _i32, _p(_vp), _p(_i32), _i32, _u64, _i32, _vp]),
     "vh_str_validate": (_i32, [_vp, _i32, _u64, _u64, _p(_i32)]),
     "vh_str_len": (_i32, [_vp, _i32, _vp, _u64, _i32, _vp]),

@@ -81,6 +81,24 @@ __device__ inline uint64_t load_slot(const void *p, int dtype, uint64_t i) {
     }
 }
 
+// a 64-bit slot as the stored element of T: float64 bits rounded to T, integers by their low bytes
+template <typename T> __device__ inline T slot_as(uint64_t v) {
+    if constexpr (std::is_floating_point_v<T>) return (T)__builtin_bit_cast(double, v);
+    else return (T)v;
+}
+
+// the store conversion of every program's result
+__device__ inline void store_slot(void *out, int dtype, uint64_t i, uint64_t v) {
+    switch (dtype) {
+    case VH_F64: static_cast<double *>(out)[i] = slot_as<double>(v); break;
+    case VH_F32: static_cast<float *>(out)[i] = slot_as<float>(v); break;
+    case VH_I64: case VH_U64: static_cast<uint64_t *>(out)[i] = slot_as<uint64_t>(v); break;
+    case VH_I32: case VH_U32: static_cast<uint32_t *>(out)[i] = slot_as<uint32_t>(v); break;
+    case VH_I16: case VH_U16: static_cast<uint16_t *>(out)[i] = slot_as<uint16_t>(v); break;
+    default: static_cast<uint8_t *>(out)[i] = slot_as<uint8_t>(v); break;
+    }
+}
+
 __device__ inline int64_t floordiv_i(int64_t a, int64_t b) {
     if (b == 0) return 0;  // numpy: 0 (with a warning)
     if (b == -1) return (int64_t)(0 - (uint64_t)a);
@@ -354,14 +372,7 @@ __global__ __launch_bounds__(EX_THREADS) void k_expr(ExprProg prog, uint64_t n, 
             if (row[r] >= n) continue;
             const uint64_t v = s[r][0];
             const uint64_t i = row[r];
-            switch (prog.out_dtype) {
-            case VH_F64: static_cast<double *>(out)[i] = as_f(v); break;
-            case VH_F32: static_cast<float *>(out)[i] = (float)as_f(v); break;
-            case VH_I64: case VH_U64: static_cast<uint64_t *>(out)[i] = v; break;
-            case VH_I32: case VH_U32: static_cast<uint32_t *>(out)[i] = (uint32_t)v; break;
-            case VH_I16: case VH_U16: static_cast<uint16_t *>(out)[i] = (uint16_t)v; break;
-            default: static_cast<uint8_t *>(out)[i] = (uint8_t)v; break;
-            }
+            store_slot(out, prog.out_dtype, i, v);
         }
     }
 }
@@ -509,6 +520,54 @@ __global__ __launch_bounds__(EX_THREADS) void k_expr_dtfield(const int64_t *col,
     }
 }
 
+// ---- fillmissing(column, constant): the shape COL(mask) CONST COL(data) WHERE ---------------
+// A masked column filled with a constant of its own dtype (expr.py `fillmissing`; the result
+// dtype is the column's).  As in k_expr_terms each lane takes 8 consecutive rows: the data by
+// load_slots8 (16-byte loads), the mask by one 8-byte load, the interpreter's WHERE on the slots
+// (a non-zero mask byte takes the constant), its store conversion (slot_as), 16-byte stores.
+// Columns of 4- and 8-byte items; a ragged tail or a misaligned block goes element by element.
+template <typename T>
+__global__ __launch_bounds__(EX_THREADS) void k_expr_fill(const void *col, int dt, const uint8_t *mask, uint64_t c,
+                                                          uint64_t n, T *out) {
+    const uint64_t stride = (uint64_t)gridDim.x * EX_THREADS * EXT_RPT;
+    for (uint64_t base = ((uint64_t)blockIdx.x * EX_THREADS + threadIdx.x) * EXT_RPT; base < n; base += stride) {
+        const uint32_t cnt = (uint32_t)min<uint64_t>(EXT_RPT, n - base);
+        uint64_t v[EXT_RPT];
+        load_slots8(col, dt, base, cnt, v);
+        uint64_t m = 0;
+        if (cnt == EXT_RPT && (reinterpret_cast<uintptr_t>(mask + base) & 7) == 0) {
+            m = *reinterpret_cast<const uint64_t *>(mask + base);
+        } else {
+            for (uint32_t r = 0; r < cnt; r++) m |= (uint64_t)mask[base + r] << (8 * r);
+        }
+        struct Rows { T e[EXT_RPT]; } rows;
+#pragma unroll
+        for (int r = 0; r < EXT_RPT; r++) rows.e[r] = slot_as<T>(((m >> (8 * r)) & 0xff) ? c : v[r]);
+        T *dst = out + base;
+        if (cnt == EXT_RPT && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+            struct Words { uint4 u[sizeof(T) * EXT_RPT / 16]; };
+            const Words w = __builtin_bit_cast(Words, rows);
+#pragma unroll
+            for (int q = 0; q < (int)(sizeof(T) * EXT_RPT / 16); q++) reinterpret_cast<uint4 *>(dst)[q] = w.u[q];
+        } else {
+            for (uint32_t r = 0; r < cnt; r++) dst[r] = rows.e[r];
+        }
+    }
+}
+
+// the program as COL(1-byte mask) CONST COL(data) WHERE with the data column's dtype as the
+// result's and 4- or 8-byte items; false: another shape
+static bool match_fill(const uint32_t *code, int ncode, const int *col_dtypes, int out_dtype, int &mcol, int &dcol, int &cidx) {
+    if (ncode != 4 || (code[0] & 0xff) != OP_COL || (code[1] & 0xff) != OP_CONST || (code[2] & 0xff) != OP_COL ||
+        (code[3] & 0xff) != OP_WHERE)
+        return false;
+    mcol = (int)(code[0] >> 8);
+    cidx = (int)(code[1] >> 8);
+    dcol = (int)(code[2] >> 8);
+    if (dtype_itemsize(col_dtypes[mcol]) != 1 || col_dtypes[dcol] != out_dtype) return false;
+    return dtype_itemsize(out_dtype) >= 4;
+}
+
 // the program as COL DT_FIELD over an int64 column, with an int32 result (a 1-byte one for
 // is_leap_year); false: another shape
 static bool match_dtfield(const uint32_t *code, int ncode, const int *col_dtypes, int out_dtype, int &unit, int &field) {
@@ -627,6 +686,21 @@ extern "C" int vh_expr_eval(const uint32_t *code, int ncode, const uint64_t *con
         const uint64_t per_block = (uint64_t)EX_THREADS * EXT_RPT;
         const unsigned grid = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)cu_count() * 8);
         hipLaunchKernelGGL(k_expr_terms, dim3(grid), dim3(EX_THREADS), 0, stream(), terms, n, static_cast<uint8_t *>(out));
+        VH_HIP(hipGetLastError());
+    } else if (int mcol = 0, dcol = 0, cidx = 0; n && !getenv_off_expr("VH_EXPR_FILL") &&
+                                                  match_fill(code, ncode, col_dtypes, out_dtype, mcol, dcol, cidx)) {
+        TimedScope ts("expr");
+        const uint64_t per_block = (uint64_t)EX_THREADS * EXT_RPT;
+        const unsigned grid = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)cu_count() * 8);
+        const uint8_t *mask = static_cast<const uint8_t *>(cols[mcol]);
+        const int dt = col_dtypes[dcol];
+        // VH_EXPR_FILL=0 (read per call) sends the shape to the interpreter: the A/B of DESIGN.md 5.27
+        switch (out_dtype) {
+        case VH_F64: hipLaunchKernelGGL(k_expr_fill<double>, dim3(grid), dim3(EX_THREADS), 0, stream(), cols[dcol], dt, mask, consts[cidx], n, static_cast<double *>(out)); break;
+        case VH_F32: hipLaunchKernelGGL(k_expr_fill<float>, dim3(grid), dim3(EX_THREADS), 0, stream(), cols[dcol], dt, mask, consts[cidx], n, static_cast<float *>(out)); break;
+        case VH_I64: case VH_U64: hipLaunchKernelGGL(k_expr_fill<uint64_t>, dim3(grid), dim3(EX_THREADS), 0, stream(), cols[dcol], dt, mask, consts[cidx], n, static_cast<uint64_t *>(out)); break;
+        default: hipLaunchKernelGGL(k_expr_fill<uint32_t>, dim3(grid), dim3(EX_THREADS), 0, stream(), cols[dcol], dt, mask, consts[cidx], n, static_cast<uint32_t *>(out)); break;
+        }
         VH_HIP(hipGetLastError());
     } else if (int unit = 0, field = 0; n && !getenv_off_expr("VH_EXPR_DTFIELD") &&
                                        match_dtfield(code, ncode, col_dtypes, out_dtype, unit, field)) {

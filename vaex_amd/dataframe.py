@@ -23,7 +23,7 @@ import numpy as np
 
 from . import agg as vagg
 from . import selections
-from .device import DeviceArray
+from .device import DeviceArray, DeviceMaskedArray
 from .strings import STRING, DeviceStringArray
 from .execution import default_executor
 from .promise import Promise, delayed
@@ -70,6 +70,11 @@ def _ensure_strings(es):
     if isinstance(es, (list, tuple)):
         return [_ensure_string(e) for e in es]
     return _ensure_string(es)
+
+
+def _literal(value):
+    """a fill value as expression text: a numpy scalar as its Python value (``repr`` of one is a call)"""
+    return repr(value.item() if isinstance(value, np.generic) else value)
 
 
 def _issequence(x):
@@ -164,6 +169,35 @@ class Expression:
         """expression.py ``Expression.astype``: the expression ``astype(x, 'dtype')``."""
         return Expression(self.df, f"astype({self.expression}, {str(np.dtype(data_type))!r})")
 
+    # the functions that consume missing values (functions.py:146-268), as expressions
+    def _missing(self, name, *args):
+        return Expression(self.df, f"{name}({', '.join([self.expression] + [_literal(a) for a in args])})")
+
+    def ismissing(self):
+        return self._missing("ismissing")
+
+    def notmissing(self):
+        return self._missing("notmissing")
+
+    def isna(self):
+        return self._missing("isna")
+
+    def notna(self):
+        return self._missing("notna")
+
+    def fillmissing(self, value):
+        return self._missing("fillmissing", value)
+
+    def fillnan(self, value):
+        return self._missing("fillnan", value)
+
+    def fillna(self, value):
+        return self._missing("fillna", value)
+
+    @property
+    def is_masked(self):
+        return self.df.is_masked(self.expression)
+
     @property
     def dtype(self):
         return self.df.data_type(self.expression)
@@ -192,7 +226,7 @@ class Expression:
 
     def to_numpy(self):
         v = self.values
-        if isinstance(v, (DeviceArray, DeviceStringArray)):
+        if isinstance(v, (DeviceArray, DeviceMaskedArray, DeviceStringArray)):
             return v.to_numpy()
         return v if np.ma.isMaskedArray(v) else np.asarray(v)  # masked columns stay masked
 
@@ -288,7 +322,58 @@ def _host_functions():
     from .datetime import FUNCTIONS
     ns = {"_ordinal_values": _ordinal_values, "astype": _astype}
     ns.update(FUNCTIONS)
+    ns.update(MISSING_FUNCTIONS)
     return ns
+
+
+# ---- the functions that consume missing values on host chunks, as the reference defines them
+# on numpy / np.ma arrays (functions.py:146-268)
+def _ismissing(x):
+    if np.ma.isMaskedArray(x):
+        return np.ma.getmaskarray(x) == 1
+    return np.zeros(len(x), dtype=bool)
+
+
+def _isnan(x):
+    """functions.py:238-251: unmasked, False at the missing rows"""
+    if np.ma.isMaskedArray(x):
+        w = x.data != x.data
+        w[np.ma.getmaskarray(x)] = False
+        return w
+    x = np.asarray(x)
+    return x != x
+
+
+def _isna(x):
+    return _isnan(x) | _ismissing(x)
+
+
+def _fill(x, mask, value, keep_mask=False):
+    if not np.any(mask):
+        return x if keep_mask or not np.ma.isMaskedArray(x) else x.data
+    ar = x.copy() if keep_mask or not np.ma.isMaskedArray(x) else x.data.copy()
+    ar[mask] = value
+    return ar
+
+
+def _fillmissing(x, value):
+    return _fill(x, _ismissing(x), value) if np.ma.isMaskedArray(x) else x
+
+
+def _fillnan(x, value):
+    """functions.py:165-179: NaN of float arrays replaced; a masked array keeps its mask"""
+    if np.ma.getdata(x).dtype.kind != "f":
+        return x
+    return _fill(x, _isnan(x), value, keep_mask=True)
+
+
+def _fillna(x, value):
+    return _fill(x, _isna(x), value)
+
+
+MISSING_FUNCTIONS = {"ismissing": _ismissing, "notmissing": lambda x: ~_ismissing(x), "isna": _isna,
+                     "notna": lambda x: ~_isna(x), "fillmissing": _fillmissing, "fillnan": _fillnan, "fillna": _fillna,
+                     "isnan": _isnan, "notnan": lambda x: ~_isnan(x)}  # what dropnan / dropna filter by
 
 
 # whether a live datetime64 / timedelta64 column holds NaT: (column reference, answer), the
@@ -330,7 +415,7 @@ class DataFrame:
         return self._filter is not None
 
     def is_device_resident(self):
-        return any(isinstance(c, (DeviceArray, DeviceStringArray)) for c in self.columns.values())
+        return any(isinstance(c, (DeviceArray, DeviceMaskedArray, DeviceStringArray)) for c in self.columns.values())
 
     def _is_string(self, expression):
         """Whether the expression is string-valued: a string column (strings.DeviceStringArray),
@@ -468,7 +553,7 @@ class DataFrame:
             filter_mask = None
         if expression in self.columns:
             col = self.columns[expression]
-            if isinstance(col, (DeviceArray, DeviceStringArray)):
+            if isinstance(col, (DeviceArray, DeviceMaskedArray, DeviceStringArray)):
                 if filter_mask is not None:
                     raise NotImplementedError("filtered DataFrames need host columns")
                 return col[i1:i2]
@@ -486,12 +571,13 @@ class DataFrame:
         ns.update(self.variables)
         for name, col in self.columns.items():
             if name in expression:
-                if isinstance(col, DeviceArray):
+                if isinstance(col, (DeviceArray, DeviceMaskedArray)):
                     raise NotImplementedError(
                         f"expression {expression!r} over an HBM column: only plain columns bin in place")
                 ns[name] = col[i1:i2]
         for name, vexpr in self.virtual_columns.items():
-            if name in expression:
+            # as a whole word: fillna's virtual column x reads the hidden column __original_x
+            if name in expression and re.search(r"(?<![\w.])%s(?!\w)" % re.escape(name), expression):
                 ns[name] = self._eval_host(vexpr, i1, i2, None)
         with np.errstate(all="ignore"):
             value = eval(expression, {"__builtins__": {}}, ns)  # noqa: S307 (host-side expressions)
@@ -509,6 +595,59 @@ class DataFrame:
         except UnsupportedExpression as e:
             raise NotImplementedError(f"expression {expression!r} over HBM columns: {e}") from None
 
+    def _eval_device_keep(self, expression, i1, i2):
+        """A boolean expression over HBM columns as a row mask (a filter, a selection): a missing
+        value selects nothing, so the program is ``value & ~mask`` (expr.Program ``keep``) and the
+        result is a plain byte mask.  Without masked operands it is the expression's own program."""
+        from .expr import UnsupportedExpression, compile_expression
+        try:
+            return compile_expression(self, expression, keep=True).evaluate(self, i1, i2)
+        except UnsupportedExpression as e:
+            raise NotImplementedError(f"expression {expression!r} over HBM columns: {e}") from None
+
+    def _eval_row_mask(self, expression, i1, i2):
+        """the device mask of a filter / selection expression: with masked columns in the frame a
+        missing value selects nothing (_eval_device_keep), else the expression's own program"""
+        if self._has_masked():
+            return self._eval_device_keep(expression, i1, i2)
+        return self._eval_device(expression, i1, i2)
+
+    def _masked_names(self):
+        """the names of the masked HBM columns (DeviceMaskedArray)"""
+        return [k for k, c in self.columns.items() if isinstance(c, DeviceMaskedArray)]
+
+    def _has_masked(self):
+        return bool(self._masked_names())
+
+    def _refuse_masked(self, what, expressions):
+        """NotImplementedError for a method that does not take missing values yet when one of the
+        expressions can be missing on an HBM frame: no number is computed as if the mask were
+        not there."""
+        if not self._has_masked():
+            return
+        for e in expressions:
+            e = _ensure_string(e)
+            if e not in (None, "", "*") and not self._is_string(e) and self.is_masked(e):
+                reads = [k for k in self._masked_names() if re.search(r"(?<![\w.])%s(?!\w)" % re.escape(k), e)]
+                raise NotImplementedError(f"{what} over the masked column {(reads or [e])[0]!r} (expression {e!r}) is "
+                                          "not supported: fillmissing / dropmissing first")
+
+    def is_masked(self, column):
+        """dataframe.py:2099: whether the column (or expression) can hold missing values: a
+        ``np.ma`` host column, a DeviceMaskedArray, or an expression whose program has a mask."""
+        column = _ensure_string(column)
+        if column in self.columns:
+            return np.ma.isMaskedArray(self.columns[column]) or isinstance(self.columns[column], DeviceMaskedArray)
+        if self.is_device_resident():
+            if self._is_string(column):
+                return False
+            from .expr import UnsupportedExpression, compile_expression
+            try:
+                return compile_expression(self, column).mask_code is not None
+            except UnsupportedExpression as e:
+                raise NotImplementedError(f"expression {column!r} over HBM columns: {e}") from None
+        return np.ma.isMaskedArray(self._eval_host(column, 0, min(self._length, 16)))
+
     def evaluate_chunk(self, expression, i1, i2, filter_mask=None):
         return self._eval_host(expression, i1, i2, filter_mask)
 
@@ -523,9 +662,9 @@ class DataFrame:
             if isinstance(v, DeviceStringArray):
                 from .superutils import mask_rows
                 return v.take(mask_rows(fm)).to_numpy()
-            if isinstance(v, DeviceArray):
+            if isinstance(v, (DeviceArray, DeviceMaskedArray)):
                 from .sort import compact_device
-                return compact_device(v, fm).to_numpy()
+                return compact_device(v, fm).to_numpy()  # a masked value: the kept rows as np.ma
             return np.asarray(v)[fm.to_numpy().astype(bool)]
         return self._eval_host(expression, i1, i2, fm)
 
@@ -536,7 +675,7 @@ class DataFrame:
             # masks per block too: _selection_mask_caches[FILTER_SELECTION_NAME],
             # dataframe.py:4161,5967, dropped by _invalidate_selection_cache)
             return self._cached_device_mask(self._filter, i1, i2)
-        return np.asarray(self._eval_host(self._filter, i1, i2), dtype=bool)
+        return self._expression_mask(self._filter, i1, i2)  # a missing value keeps nothing, as in a selection
 
     def _cached_device_mask(self, expr, i1, i2, compute=None):
         # An entry is (key, column references, variable values, mask).  A hit needs the frame's
@@ -555,7 +694,7 @@ class DataFrame:
                     return m
         # expr: the expression string, or (with compute) the hashable form of a selection that
         # is evaluated node by node
-        m = self._eval_device(expr, i1, i2) if compute is None else compute()
+        m = self._eval_row_mask(expr, i1, i2) if compute is None else compute()
         with _mask_cache_lock:
             if len(cache) >= 8:
                 del cache[:]
@@ -628,8 +767,16 @@ class DataFrame:
         if not parts:
             return None
         expr = " & ".join(parts)
+        if invert and self._has_masked():
+            # a missing value selects nothing: the skip mask is ~(value & ~mask), so the keep
+            # program is complemented as a mask, not the expression before it is compiled
+            from .superutils import mask_combine
+
+            def compute():
+                return mask_combine(self._eval_device_keep(expr, i1, i2), None)
+            return self._cached_device_mask(("skip", expr), i1, i2, compute) if cache else compute()
         expr = f"~({expr})" if invert else expr
-        return self._cached_device_mask(expr, i1, i2) if cache else self._eval_device(expr, i1, i2)
+        return self._cached_device_mask(expr, i1, i2) if cache else self._eval_row_mask(expr, i1, i2)
 
     def _device_selection_mask(self, selection, i1, i2, invert, cache):
         from .superutils import mask_combine
@@ -736,6 +883,54 @@ class DataFrame:
         column_names = _ensure_strings(list(column_names or self.columns))
         self._selection(lambda current: selections.SelectionDropNa(drop_nan, drop_masked, column_names, current, mode),
                         name)
+
+    def _drop(self, column_names, missing, nan):
+        """dataframe.py:4750-4789 ``_filter_all``: a copy whose filter also asks every named column
+        (default: every real column) to be there: ``notmissing(c)`` for the columns that can be
+        missing, ``~isnan(c)`` for the float ones -- a conjunction, so on an HBM frame the filter
+        stays one device program."""
+        names = _ensure_strings(list(column_names)) if column_names is not None else list(self.columns)
+        terms = []
+        for c in names:
+            if self._is_string(c):
+                continue  # string columns hold neither nulls nor NaN
+            if missing and self.is_masked(c):
+                terms.append(f"notmissing({c})")
+            if nan and self.data_type(c).kind == "f":
+                terms.append(f"~isnan({c})")
+        return self.filter(" & ".join(terms)) if terms else self.copy()
+
+    def dropmissing(self, column_names=None):
+        """dataframe.py:4750: the rows without a missing value in ``column_names``."""
+        return self._drop(column_names, True, False)
+
+    def dropnan(self, column_names=None):
+        """dataframe.py:4758: the rows without a NaN in ``column_names``."""
+        return self._drop(column_names, False, True)
+
+    def dropna(self, column_names=None):
+        """dataframe.py:4766: the rows with neither a missing value nor a NaN in ``column_names``."""
+        return self._drop(column_names, True, True)
+
+    def fillna(self, value, column_names=None, prefix="__original_", inplace=False):
+        """dataframe.py:4595: missing values and NaN of the named columns (default: every real
+        column that can hold either) replaced by ``value``.  Each such column becomes the virtual
+        column ``fillna(__original_<name>, value)``; the original moves to that hidden name, so
+        no data is lost.  On an HBM frame the value must fit the column's dtype (expr.py
+        ``fillmissing``)."""
+        df = self if inplace else self.copy()
+        names = _ensure_strings(list(column_names)) if column_names is not None else list(df.columns)
+        for name in names:
+            if name not in df.columns:
+                raise KeyError(f"fillna: {name!r} is not a real column")
+            if df._is_string(name) or name.startswith(prefix):
+                continue
+            if column_names is None and not (df.is_masked(name) or df.data_type(name).kind == "f"):
+                continue  # holds neither missing values nor NaN
+            hidden = prefix + name
+            df.columns = {(hidden if k == name else k): v for k, v in df.columns.items()}
+            df.virtual_columns[name] = f"fillna({hidden}, {_literal(value)})"
+        return df
 
     def select_rectangle(self, x, y, limits, mode="replace", name="default"):
         """dataframe.py:4794-4806: ``select_box([x, y], [(x1, x2), (y1, y2)])``."""
@@ -905,6 +1100,7 @@ class DataFrame:
         waslist, [expressions] = listify(_ensure_strings(expression))
         binbys = binby if isinstance(binby, (list, tuple)) else [binby]
         binbys = [str(b) for b in _ensure_strings(binbys) if b is not None and str(b) != ""]
+        self._refuse_masked("percentile_approx / median_approx", expressions + binbys)
         waslist_percentage, [percentages] = listify(percentage)
         percentages = [float(p) for p in percentages]
         sel = None if selection in (None, False) else selection
@@ -965,6 +1161,7 @@ class DataFrame:
             if not _issequence(pair) or len(pair) != 2:
                 raise ValueError("mutual_information wants pairs of expressions, not %r" % (pair,))
         pairs = [_ensure_strings(list(pair)) for pair in pairs]
+        self._refuse_masked("mutual_information", [e for pair in pairs for e in pair] + list(listify(binby)[1][0]))
 
         def one_pair_limits(value):  # [xlim, ylim], each None, a string or [lo, hi]
             return _issequence(value) and len(value) == 2 and all(
@@ -1144,6 +1341,7 @@ class DataFrame:
         covariance matrices ``outer + (N, N)`` (one pass over the columns for all of them)."""
         from . import hostops
         sel = None if selection is False else selection
+        self._refuse_masked("cov / covar / correlation", [e for expressions in pairs for e in expressions] + list(listify(binby)[1][0]))
         binners = self._create_binners(binby, limits, shape, selection=sel)
         results = []
         for expressions in pairs:
@@ -1318,7 +1516,10 @@ class DataFrame:
                 return keys
             # dataframe.py:563-578: map_ordinal over every row of the frame
             values = self.evaluate(expression, filtered=False)
-            if isinstance(values, DeviceArray):
+            if isinstance(values, DeviceMaskedArray):
+                inverse = ordered_set.map_ordinal(values.data).to_numpy().astype(np.int64)
+                inverse[values.mask.to_numpy().astype(bool)] = ordered_set.null_value
+            elif isinstance(values, DeviceArray):
                 inverse = ordered_set.map_ordinal(values).to_numpy().astype(np.int64)
             else:
                 inverse = ordered_set.map_ordinal(values).astype(np.int64)
@@ -1538,10 +1739,12 @@ class DataFrame:
         """dataframe.py export_hdf5: numeric columns (host or HBM) as vaex's HDF5 layout
         version 2, contiguous and 4 KiB aligned so the file maps back without copies."""
         from .hdf5 import export_hdf5
+        self._refuse_export()
         export_hdf5(self, path)
 
     def export_arrow(self, path, **kwargs):
         import pyarrow as pa
+        self._refuse_export()
         cols = {}
         for name in self.get_column_names():
             v = self.columns.get(name)
@@ -1551,6 +1754,10 @@ class DataFrame:
             table = pa.table(cols)
             with pa.ipc.new_file(sink, table.schema) as w:
                 w.write_table(table)
+
+    def _refuse_export(self):
+        if self._has_masked():
+            raise NotImplementedError(f"export of the masked HBM column {self._masked_names()[0]!r} is not supported")
 
     def binby(self, by=None, agg=None, sort=False, copy=True, delay=False, progress=None):
         from .groupby import BinBy
@@ -1563,7 +1770,7 @@ class DataFrame:
     def to_dict(self):
         out = {}
         for k, v in self.columns.items():
-            out[k] = v.to_numpy() if isinstance(v, DeviceArray) else np.asarray(v)
+            out[k] = v.to_numpy() if isinstance(v, (DeviceArray, DeviceMaskedArray)) else np.asarray(v)
         return out
 
     def __repr__(self):
@@ -1574,7 +1781,7 @@ def from_arrays(**arrays):
     """vaex.from_arrays: numpy arrays (host) or DeviceArray (HBM-resident) columns."""
     cols = {}
     for k, v in arrays.items():
-        if isinstance(v, (DeviceArray, DeviceStringArray)) or np.ma.isMaskedArray(v):
+        if isinstance(v, (DeviceArray, DeviceMaskedArray, DeviceStringArray)) or np.ma.isMaskedArray(v):
             cols[k] = v
         else:
             cols[k] = np.asarray(v)

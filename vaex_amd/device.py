@@ -110,5 +110,128 @@ class DeviceArray:
         return f"DeviceArray(length={self.length}, dtype={self.dtype})"
 
 
+class DeviceMaskedArray:
+    """An HBM column with missing values: ``data`` (a DeviceArray) and ``mask`` (a DeviceArray of
+    uint8 or bool, 1 = missing: numpy's convention, the one ``set_data_mask`` takes), of one
+    length.  The mask holds 0 and 1 only (what ``from_numpy``, ``from_arrow`` and every expression
+    write): the engine counts bytes equal to 1 as set, so any other value is undefined.  The data
+    under a missing row is unspecified.  Deliberately not a DeviceArray: code
+    that has not been taught about masks fails its ``isinstance`` check instead of dropping one."""
+
+    def __init__(self, data, mask):
+        if not isinstance(data, DeviceArray) or not isinstance(mask, DeviceArray):
+            raise TypeError("DeviceMaskedArray(data, mask) takes two DeviceArrays")
+        if mask.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+            raise TypeError(f"the mask is uint8 or bool, not {mask.dtype}")
+        if len(mask) != len(data):
+            raise ValueError(f"data holds {len(data)} rows, the mask {len(mask)}")
+        self.data = data
+        self.mask = mask
+
+    # ---- construction -------------------------------------------------------
+    @classmethod
+    def from_numpy(cls, ar):
+        """A numpy (masked) array; ``np.ma.nomask`` and a plain array give an all-zero mask."""
+        mask = np.ma.getmaskarray(ar) if np.ma.isMaskedArray(ar) else np.zeros(len(ar), bool)
+        return cls(DeviceArray.from_numpy(np.ma.getdata(ar)), DeviceArray.from_numpy(mask.view(np.uint8)))
+
+    @classmethod
+    def from_arrow(cls, ar):
+        """A primitive numeric / bool ``pyarrow.Array`` with or without nulls.  The values buffer
+        and the validity bitmap are uploaded as they are (the bitmap: n / 8 bytes) and the byte
+        mask is expanded on the device (``vh_mask_unpack_bits``); the array's offset is honoured."""
+        import pyarrow as pa
+        if isinstance(ar, pa.ChunkedArray):
+            ar = ar.combine_chunks()
+        t = ar.type
+        n, offset = len(ar), ar.offset
+        validity, values = ar.buffers()[:2] if len(ar.buffers()) == 2 else (None, None)
+        if not (pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_boolean(t)) or values is None:
+            raise TypeError(f"from_arrow takes primitive numeric / bool arrays, not {t}")
+        if pa.types.is_boolean(t):  # bit-packed values: expanded like the bitmap, then inverted
+            packed = np.frombuffer(values, np.uint8)[offset // 8:(offset + n + 7) // 8]
+            data = DeviceArray.empty(n, np.bool_)
+            if n:
+                bits = DeviceArray.from_numpy(packed)
+                _lib.call("vh_mask_unpack_bits", bits.ptr, offset % 8, n, data.ptr)
+                _lib.call("vh_mask_combine", data.ptr, None, 0, n, data.ptr)
+        else:
+            dtype = np.dtype(t.to_pandas_dtype())
+            if dtype.itemsize not in (1, 2, 4, 8) or dtype.kind not in "iuf" or dtype == np.float16:
+                raise TypeError(f"from_arrow: {t}")
+            data = DeviceArray.from_numpy(np.frombuffer(values, dtype)[offset:offset + n])
+        mask = DeviceArray.empty(n, np.uint8)
+        if validity is None or ar.null_count == 0:
+            if n:
+                _lib.call("vh_memset", mask.ptr, 0, n)
+        else:
+            bits = DeviceArray.from_numpy(np.frombuffer(validity, np.uint8)[offset // 8:(offset + n + 7) // 8])
+            _lib.call("vh_mask_unpack_bits", bits.ptr, offset % 8, n, mask.ptr)
+        _lib.synchronize()  # the uploaded bitmaps are freed on return
+        return cls(data, mask)
+
+    # ---- views / copies -----------------------------------------------------
+    @property
+    def dtype(self):
+        return self.data.dtype
+
+    @property
+    def length(self):
+        return self.data.length
+
+    @property
+    def nbytes(self):
+        return self.data.nbytes + self.mask.nbytes
+
+    @property
+    def ndim(self):
+        return 1
+
+    @property
+    def shape(self):
+        return (self.data.length,)
+
+    def __len__(self):
+        return self.data.length
+
+    def __getitem__(self, item):
+        return DeviceMaskedArray(self.data[item], self.mask[item])
+
+    @property
+    def null_count(self):
+        """the number of missing rows (a device reduction over the mask)"""
+        count = ctypes.c_uint64()
+        _lib.call("vh_mask_count", self.mask.ptr, len(self), ctypes.byref(count))
+        return count.value
+
+    def to_numpy(self, pinned=False):
+        return np.ma.array(self.data.to_numpy(pinned=pinned), mask=self.mask.to_numpy().astype(bool), shrink=False)
+
+    def to_arrow(self):
+        """A ``pyarrow.Array`` of the column; the validity bitmap is packed on the device
+        (``vh_mask_pack_bits``) and read back as n / 8 bytes."""
+        import pyarrow as pa
+        n = len(self)
+        bits = DeviceArray.empty((n + 7) // 8, np.uint8)
+        if n:
+            _lib.call("vh_mask_pack_bits", self.mask.ptr, n, bits.ptr)
+        validity = pa.py_buffer(bits.to_numpy().tobytes())
+        data = self.data.to_numpy()
+        if self.dtype.kind == "b":
+            return pa.Array.from_buffers(pa.bool_(), n, [validity, pa.py_buffer(np.packbits(data, bitorder="little").tobytes())])
+        return pa.Array.from_buffers(pa.from_numpy_dtype(self.dtype), n, [validity, pa.py_buffer(data.tobytes())])
+
+    def __array__(self, dtype=None, copy=None):
+        raise TypeError("a DeviceMaskedArray does not convert to a plain array (its mask would be dropped): to_numpy()")
+
+    def __repr__(self):
+        return f"DeviceMaskedArray(length={len(self)}, dtype={self.dtype})"
+
+
+def is_masked_column(col):
+    """a host ``np.ma`` column or a masked HBM column: the routes that take neither ask this"""
+    return np.ma.isMaskedArray(col) or isinstance(col, DeviceMaskedArray)
+
+
 def is_device_array(x):
     return isinstance(x, DeviceArray)

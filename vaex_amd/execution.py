@@ -144,6 +144,9 @@ class ExecutorLocal:
         start, end = self.row_range(df)
         chunk_size = self.chunk_size_for(df)
         try:
+            if getattr(self, "world", 1) > 1 and df._has_masked():
+                raise NotImplementedError(f"masked HBM column {df._masked_names()[0]!r} with a multi-rank executor is "
+                                          "not supported")
             for i1 in range(start, end, chunk_size):
                 i2 = min(end, i1 + chunk_size)
                 filter_mask = df.evaluate_filter_mask(i1, i2) if df.filtered else None

@@ -19,6 +19,14 @@ the float64 result rounded once), exact where the result is NaN, infinite or zer
 casts of NaN, infinities or values outside the target type, negative shift counts, integer
 ``**`` with a negative exponent in a column.
 
+Missing values: a masked HBM column (``device.DeviceMaskedArray``) binds its data and its mask
+(a bool column, 1 = missing).  Every node carries an optional mask program over the same inputs:
+a result is missing where a masked input the node reads is, ``where`` follows the chosen branch,
+and ``ismissing / notmissing / isna / notna / isnan / fillmissing / fillnan / fillna`` consume
+masks (:data:`MISSING_FUNCTIONS`).  ``Program.mask_code`` is that program (None: never missing);
+a boolean compiled as a row mask (``keep``) is ``value & ~mask``.  No domain masks are added and
+``where`` keeps masks: this is not ``np.ma``.
+
 Supported: columns, virtual columns, variables, Python int / float / bool
 constants, ``+ - * / // % **``, unary ``- ~``, comparisons (chained too), ``& | ^ << >>``,
 ``and / or / not`` on booleans, and the functions in :data:`FUNCTIONS` (also as ``np.f``).
@@ -98,7 +106,9 @@ def column_has_nat(col):
     from the device min / max pass over its int64 bits; that pass reports float64, in which the
     512 values from INT64_MIN up are one number, so a minimum that low is settled exactly by a
     device `== INT64_MIN` mask and its maximum."""
-    from .device import DeviceArray
+    from .device import DeviceArray, DeviceMaskedArray
+    if isinstance(col, DeviceMaskedArray):
+        col = col.data  # NaT is not a mask: one under a missing row refuses the column as well
     if not isinstance(col, DeviceArray):
         return bool(np.isnat(np.asarray(col)).any())
     n = len(col)
@@ -122,10 +132,14 @@ class _Typed:
     """A compiled sub-expression: its code and numpy dtype (or a Python scalar for a
     constant, which numpy 2 promotes as a weak scalar)."""
 
-    def __init__(self, code, dtype, scalar=None):
+    def __init__(self, code, dtype, scalar=None, mask=None, own_mask=False):
         self.code = code
         self.dtype = np.dtype(dtype)
         self.scalar = scalar  # the Python value of a constant leaf
+        # the mask program: None (never missing), or the distinct bool sub-programs (tuples of
+        # instructions over the same inputs) whose OR is 1 on the rows where the value is missing
+        self.mask = mask
+        self.own_mask = own_mask  # the node set its mask itself (where, the mask consumers)
 
     @property
     def proto(self):
@@ -137,12 +151,35 @@ def _kind(dt):
     return "f" if dt.kind == "f" else ("u" if dt.kind == "u" else ("b" if dt.kind == "b" else "i"))
 
 
+# the functions that consume masks (the reference's functions.py:146-268): name -> arguments
+MISSING_FUNCTIONS = {"ismissing": 1, "notmissing": 1, "isna": 1, "notna": 1, "fillmissing": 2, "fillnan": 2, "fillna": 2}
+
+
+def _mask_or(*masks):
+    """the OR of mask programs: their distinct terms in order of first use, None for none"""
+    out = []
+    for m in masks:
+        for term in m or ():
+            if term not in out:
+                out.append(term)
+    return tuple(out) or None
+
+
+def _mask_code(mask):
+    """the instructions of a mask program: its terms joined by OR_I"""
+    code = []
+    for k, term in enumerate(mask):
+        code += list(term) + ([OP["OR_I"]] if k else [])
+    return code
+
+
 class Compiler:
     def __init__(self, df):
         self.df = df
         self.columns = []      # column names in slot order
         self.consts = []       # uint64 bit patterns
         self._depth = 0
+        self._masks = {}       # id(ast node) -> (node, mask program) of every node visited
 
     # ---- leaves -------------------------------------------------------------------
     def _const(self, value):
@@ -287,6 +324,8 @@ class Compiler:
             raise UnsupportedExpression(f"column {name!r} of dtype {dt}")
         if np.ma.isMaskedArray(col):
             raise UnsupportedExpression(f"masked column {name!r}")
+        from .device import DeviceMaskedArray
+        masked = isinstance(col, DeviceMaskedArray)
         if dt.kind in "mM":
             # a program has one result dtype and does plain int64 arithmetic: pandas answers NaT
             # rows with NaN, numpy propagates NaT, so only NaT-free columns compute here
@@ -297,7 +336,15 @@ class Compiler:
             if len(self.columns) >= MAX_COLS:
                 raise UnsupportedExpression("too many columns")
             self.columns.append(name)
-        return _Typed([OP["COL"] | self.columns.index(name) << 8], dt)
+        mask = None
+        if masked:  # the mask is one more input: a bool column
+            key = ("mask", name)
+            if key not in self.columns:
+                if len(self.columns) >= MAX_COLS:
+                    raise UnsupportedExpression("too many columns")
+                self.columns.append(key)
+            mask = ((OP["COL"] | self.columns.index(key) << 8,),)
+        return _Typed([OP["COL"] | self.columns.index(name) << 8], dt, mask=mask)
 
     # ---- conversions -----------------------------------------------------------------
     def _to_float(self, t, dt):
@@ -345,7 +392,14 @@ class Compiler:
         m = getattr(self, "v_" + type(node).__name__, None)
         if m is None:
             raise UnsupportedExpression(f"unsupported syntax {type(node).__name__}")
-        return m(node)
+        t = m(node)
+        if not (t.own_mask or isinstance(node, (ast.Name, ast.Expression))):
+            # propagation: missing where an operand the node reads is missing
+            mask = _mask_or(*[self._masks[id(c)][1] for c in ast.iter_child_nodes(node) if id(c) in self._masks])
+            if mask != t.mask:
+                t = _Typed(t.code, t.dtype, t.scalar, mask)
+        self._masks[id(node)] = (node, t.mask)
+        return t
 
     def v_Expression(self, node):
         return self.visit(node.body)
@@ -626,6 +680,8 @@ class Compiler:
                 return self._const(make(*values))
             except (ValueError, TypeError) as e:
                 raise UnsupportedExpression(f"{name}: {e}")
+        if name in MISSING_FUNCTIONS:
+            return self._missing_call(name, node.args)
         args = [self.visit(a) for a in node.args]
         if name.startswith("dt_") and name[3:] in DT_FIELDS and len(args) == 1:
             a = args[0]
@@ -650,9 +706,15 @@ class Compiler:
             return _Typed(self._finish(self._to_float(a, dt) + [OP[op]], dt), dt)
         if name in PREDICATES and len(args) == 1:
             a = args[0]
+            # isnan consumes the mask (functions.py:238-251: unmasked, False at missing rows);
+            # isfinite / isinf propagate it
+            own = name == "isnan"
             if a.dtype.kind != "f":  # integers are never nan / inf: a constant column
-                return _Typed(self._const(name == "isfinite").code, np.bool_)
-            return _Typed(a.code + [OP[PREDICATES[name][1]]], np.bool_)
+                return _Typed(self._const(name == "isfinite").code, np.bool_, own_mask=own)
+            code = a.code + [OP[PREDICATES[name][1]]]
+            if own and a.mask:
+                code += _mask_code(a.mask) + [OP["NOT_B"], OP["AND_I"]]
+            return _Typed(code, np.bool_, own_mask=own)
         if name in ("abs", "absolute", "fabs") and len(args) == 1:
             a = args[0]
             if a.dtype.kind == "f" or name == "fabs":
@@ -695,8 +757,60 @@ class Compiler:
                 code = c.code + self._to_float(a, dt) + self._to_float(b, dt) + [OP["WHERE"]]
             else:
                 code = c.code + a.code + b.code + [OP["WHERE"]]
-            return _Typed(self._finish(code, dt), dt)
+            # missing where the condition is, and otherwise where the chosen branch is
+            mask = c.mask
+            if a.mask or b.mask:
+                false = self._const(False).code
+                term = c.code + (_mask_code(a.mask) if a.mask else false) + (_mask_code(b.mask) if b.mask else false)
+                mask = _mask_or(mask, (tuple(term + [OP["WHERE"]]),))
+            return _Typed(self._finish(code, dt), dt, mask=mask, own_mask=True)
         raise UnsupportedExpression(f"function {name}")
+
+    def _fill_const(self, name, dt, value):
+        """the code of the fill value in the column's dtype, converted as numpy's assignment
+        ``ar[mask] = value`` converts it; a value the dtype cannot hold is refused"""
+        if isinstance(value, np.generic):
+            value = value.item()
+        if not isinstance(value, (bool, int, float)):
+            raise UnsupportedExpression(f"{name}: the value is an int, float or bool, not {value!r}")
+        ar = np.zeros(1, dt)
+        with np.errstate(all="ignore"):
+            try:
+                ar[np.array([True])] = value
+            except (OverflowError, TypeError, ValueError) as e:
+                raise UnsupportedExpression(f"{name}: {value!r} does not fit {dt}: {e}")
+        got = ar[0].item()
+        if dt.kind in "iub" and got != value:  # numpy truncates 1.5 to 1 and takes 2 for True silently
+            raise UnsupportedExpression(f"{name}: {dt} cannot hold {value!r}")
+        return list(self._const(got).code)
+
+    def _missing_call(self, name, nodes):
+        """ismissing / notmissing / isna / notna (unmasked booleans; the constants for an unmasked
+        argument without NaN), fillmissing / fillna (unmasked, the argument's dtype) and fillnan
+        (NaN of float nodes replaced, the mask kept), in the existing opcodes."""
+        if len(nodes) != MISSING_FUNCTIONS[name]:
+            raise UnsupportedExpression(f"{name} takes {MISSING_FUNCTIONS[name]} argument(s)")
+        a = self.visit(nodes[0])
+        if a.dtype.kind in "mM":
+            raise UnsupportedExpression(f"{name} of a datetime64 / timedelta64 value")
+        missing = _mask_code(a.mask) if a.mask else None
+        nan = list(a.code) + [OP["ISNAN"]] if a.dtype.kind == "f" else None
+        na = nan + missing + [OP["OR_I"]] if nan and missing else (nan or missing)
+        if name in ("ismissing", "notmissing", "isna", "notna"):
+            cond = missing if name.endswith("missing") else na
+            negate = name.startswith("not")
+            if cond is None:
+                return _Typed(self._const(negate).code, np.bool_, own_mask=True)
+            return _Typed(cond + ([OP["NOT_B"]] if negate else []), np.bool_, own_mask=True)
+        v = self.visit(nodes[1])
+        if v.scalar is None or a.scalar is not None:
+            raise UnsupportedExpression(f"{name}(x, value): x is a column expression, value a constant or a variable")
+        fill = self._fill_const(name, a.dtype, v.scalar)
+        cond = {"fillmissing": missing, "fillnan": nan, "fillna": na}[name]
+        mask = a.mask if name == "fillnan" else None
+        if cond is None:
+            return _Typed(list(a.code), a.dtype, mask=mask, own_mask=True)
+        return _Typed(cond + fill + list(a.code) + [OP["WHERE"]], a.dtype, mask=mask, own_mask=True)
 
     def _string_call(self, name, node):
         """``str_len(s)`` / ``str_byte_length(s)`` / ``str_<predicate>(s, 'literal')`` over a string
@@ -804,9 +918,13 @@ def _stack_depth(code):
 
 
 class Program:
-    """A compiled expression: evaluate(df, i1, i2) -> DeviceArray of ``dtype``."""
+    """A compiled expression: evaluate(df, i1, i2) -> DeviceArray of ``dtype``, or a
+    DeviceMaskedArray when the result can be missing (``mask_code`` is set: a bool program over
+    the same inputs and constants, 1 = missing).  keep: the expression is wanted as a row mask
+    (a filter, a selection): a missing value selects nothing, so the program is ``value & ~mask``
+    and has no mask program."""
 
-    def __init__(self, df, expression):
+    def __init__(self, df, expression, keep=False):
         self.expression = str(expression)
         c = Compiler(df)
         try:
@@ -815,39 +933,60 @@ class Program:
             raise UnsupportedExpression(str(e))
         t = c.visit(tree)
         code = list(t.code)  # a constant expression is broadcast by the kernel
-        if len(code) > MAX_CODE:
-            raise UnsupportedExpression("expression too long for the device program")
-        if _stack_depth(code) > MAX_DEPTH:
-            raise UnsupportedExpression("expression too deeply nested")
-        # keep the constants that the program uses, in the order of first use
+        mask_code = _mask_code(t.mask) if t.mask else None
+        if keep and mask_code is not None:
+            if t.dtype.kind != "b":
+                raise UnsupportedExpression(f"a row mask is boolean, not {t.dtype}")
+            # value & (m == 0) & ...: a conjunction of comparisons stays one (the shape of the
+            # comparison-terms kernel); any other mask term is negated as it is
+            zero = c._const(0).code
+            for term in t.mask:
+                if len(term) == 1 and term[0] & 0xFF == OP["COL"]:
+                    code += list(term) + zero + [OP["EQ_I"], OP["AND_I"]]
+                else:
+                    code += list(term) + [OP["NOT_B"], OP["AND_I"]]
+            mask_code = None
+        for prog in (code, mask_code or []):
+            if len(prog) > MAX_CODE:
+                raise UnsupportedExpression("expression too long for the device program")
+            if _stack_depth(prog) > MAX_DEPTH:
+                raise UnsupportedExpression("expression too deeply nested")
+        # keep the constants that the programs use, in the order of first use
         used = []
-        for k, ins in enumerate(code):
-            if ins & 0xFF == OP["CONST"]:
-                if ins >> 8 not in used:
-                    used.append(ins >> 8)
-                code[k] = OP["CONST"] | used.index(ins >> 8) << 8
+        for prog in (code, mask_code or []):
+            for k, ins in enumerate(prog):
+                if ins & 0xFF == OP["CONST"]:
+                    if ins >> 8 not in used:
+                        used.append(ins >> 8)
+                    prog[k] = OP["CONST"] | used.index(ins >> 8) << 8
         if len(used) > MAX_CONST:
             raise UnsupportedExpression("too many constants")
         self.code = code
+        self.mask_code = mask_code
         self.consts = [c.consts[k] for k in used]
         self.columns = list(c.columns)
         self.dtype = t.dtype  # bool results are 0 / 1 bytes (numpy bool)
         self.is_bool = t.dtype.kind == "b"
 
     def evaluate(self, df, i1, i2, out=None):
-        from .device import DeviceArray
+        from .device import DeviceArray, DeviceMaskedArray
         n = i2 - i1
         cols = []
         keep = []
         strings = {}  # the transformed sources of this evaluation, each computed once
         for name in self.columns:
+            if isinstance(name, tuple) and name[0] == "mask":  # a masked column's mask (Compiler._column)
+                cols.append(df.columns[name[1]].mask[i1:i2])
+                continue
             if isinstance(name, tuple):  # a string function's column (Compiler._string_input)
                 _, fn, source, arg = name
                 scol = evaluate_string(df, source, i1, i2, strings)
                 cols.append(scol.match(fn, arg) if arg is not None else scol.len(fn))
                 continue
             col = df.columns[name]
-            if not isinstance(col, DeviceArray):
+            if isinstance(col, DeviceMaskedArray):
+                col = col.data[i1:i2]
+            elif not isinstance(col, DeviceArray):
                 col = DeviceArray.from_numpy(np.ascontiguousarray(col[i1:i2]))
                 keep.append(col)
             else:
@@ -856,12 +995,20 @@ class Program:
         if out is None:
             out = DeviceArray.empty(n, self.dtype)
         k = max(1, len(cols))
-        code = (ctypes.c_uint32 * len(self.code))(*self.code)
         consts = (ctypes.c_uint64 * max(1, len(self.consts)))(*self.consts)
         ptrs = (ctypes.c_void_p * k)(*[c.ptr for c in cols])
         dts = (ctypes.c_int * k)(*[_lib.dtype_code(c.dtype)[0] for c in cols])
+        code = (ctypes.c_uint32 * len(self.code))(*self.code)
         _lib.call("vh_expr_eval", code, len(self.code), consts, len(self.consts), ptrs, dts, len(cols), n,
                   _lib.dtype_code(self.dtype)[0], out.ptr)
+        if self.mask_code is not None:
+            # the mask program: a second launch of the same kernel over the same inputs (its
+            # input bytes do not overlap the value program's: one pass would save only a launch)
+            mask = DeviceArray.empty(n, np.uint8)
+            code = (ctypes.c_uint32 * len(self.mask_code))(*self.mask_code)
+            _lib.call("vh_expr_eval", code, len(self.mask_code), consts, len(self.consts), ptrs, dts, len(cols), n,
+                      _lib.DTYPE_CODE["uint8"], mask.ptr)
+            out = DeviceMaskedArray(out, mask)
         if keep:
             _lib.synchronize()  # the staged columns are freed on return
         return out
@@ -909,11 +1056,13 @@ def evaluate_string(df, plan, i1, i2, memo=None):
 _CACHE = {}
 
 
-def compile_expression(df, expression):
-    """The Program of ``expression`` on ``df`` (cached per frame structure)."""
-    key = (id(df), str(expression), tuple(sorted(df.virtual_columns.items())),
+def compile_expression(df, expression, keep=False):
+    """The Program of ``expression`` on ``df`` (cached per frame structure); keep: as a row mask
+    (``Program``)."""
+    from .device import DeviceMaskedArray
+    key = (id(df), str(expression), bool(keep), tuple(sorted(df.virtual_columns.items())),
            tuple(sorted((k, repr(v)) for k, v in df.variables.items() if np.isscalar(v))),
-           tuple((k, str(getattr(v, "dtype", ""))) for k, v in df.columns.items()))
+           tuple((k, str(getattr(v, "dtype", "")), isinstance(v, DeviceMaskedArray)) for k, v in df.columns.items()))
     p = _CACHE.get(key)
     if p is not None:
         for name in p.columns:  # the key names dtypes, not column objects: a new column may hold NaT
@@ -922,7 +1071,7 @@ def compile_expression(df, expression):
             if np.dtype(df.columns[name].dtype).kind in "mM" and df._column_has_nat(name):
                 raise UnsupportedExpression(f"column {name!r} holds NaT (not-a-time) values")
     if p is None:
-        p = Program(df, expression)
+        p = Program(df, expression, keep=keep)
         if len(_CACHE) > 256:
             _CACHE.clear()
         _CACHE[key] = p

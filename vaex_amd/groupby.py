@@ -43,6 +43,7 @@ class BinnerTime(BinnerBase):
         self.sort_indices = None
         self.expression = self.df[str(expression)]
         self.label = str(self.expression)
+        self.df._refuse_masked("BinnerTime", [self.label])
         self.tmin, self.tmax = self.expression.minmax()
         self.resolution_type = "M8[%s]" % self.resolution
         tmin, tmax = self.tmin.astype(self.resolution_type), self.tmax.astype(self.resolution_type)
@@ -186,6 +187,9 @@ SPECULATE_MIN_ROWS = 1 << 22
 SPECULATE_SAMPLE = 1 << 16
 
 
+from .device import is_masked_column as _masked  # noqa: E402  (np.ma and DeviceMaskedArray keys take the set-grouper route)
+
+
 class DenseRangeMiss(Exception):
     """A speculative dense range missed keys (the grid's under/overflow cells are not empty)."""
 
@@ -218,7 +222,7 @@ def _dense_range(df, expression, speculative=False):
     True; GroupBy.agg raises DenseRangeMiss when rows fall outside it."""
     expression = str(expression)
     col = df.columns.get(expression)
-    if col is None or np.ma.isMaskedArray(col):
+    if col is None or _masked(col):
         return None
     dtype = np.dtype(col.dtype)
     if dtype.kind not in "iu":
@@ -290,7 +294,7 @@ def _key_ranges(df, by):
             return None
         name = str(b)
         col = df.columns.get(name)
-        if col is None or df.is_category(name) or np.ma.isMaskedArray(col) or name in names:
+        if col is None or df.is_category(name) or _masked(col) or name in names:
             return None
         dt = np.dtype(col.dtype)
         if dt.kind not in "iu" or not dt.isnative or (isinstance(col, np.ndarray) and col.ndim != 1):
@@ -395,7 +399,7 @@ def _groupby_combine_sets(df, by, agg, sort=False, row_limit=None, combine=True)
     ``combine='auto'`` decides from the set sizes, as the reference does (rows / cells < 10
     combines; otherwise the cartesian grid of these groupers).  Returns None for categorical
     or binner keys (the caller's cartesian GroupBy)."""
-    from .device import DeviceArray
+    from .device import DeviceArray, DeviceMaskedArray
     if any(isinstance(b, BinnerBase) or not isinstance(b, (str, Expression)) or df.is_category(b) for b in by):
         return None
     names = [str(b) for b in by]
@@ -414,7 +418,11 @@ def _groupby_combine_sets(df, by, agg, sort=False, row_limit=None, combine=True)
         mask = np.ma.getmaskarray(col) if np.ma.isMaskedArray(col) else None
         if np.ma.isMaskedArray(col):
             col = col.data
-        ords = g.set.map_ordinal(col if isinstance(col, DeviceArray) else np.ascontiguousarray(col))
+        if isinstance(col, DeviceMaskedArray):
+            # a masked HBM key: where(mask, null_value, map_ordinal(data)), on the device
+            ords = _device_where(col.mask, g.null_value, g.set.map_ordinal(col.data))
+        else:
+            ords = g.set.map_ordinal(col if isinstance(col, DeviceArray) else np.ascontiguousarray(col))
         if mask is not None and mask.any():
             ords = np.array(ords, copy=True)
             ords[mask] = g.null_value
@@ -440,6 +448,22 @@ def _groupby_combine_sets(df, by, agg, sort=False, row_limit=None, combine=True)
         if not name.startswith("__vaex_amd_ordinal_"):
             columns[name] = values
     return DataFrame(columns)
+
+
+def _device_where(mask, value, column):
+    """``where(mask, value, column)`` for a device byte mask, an integer and an integer
+    DeviceArray, as a new DeviceArray of the column's dtype (one launch of the expression kernel)."""
+    import ctypes
+    from . import _lib
+    from .device import DeviceArray
+    from .expr import OP
+    out = DeviceArray.empty(len(column), column.dtype)
+    code = (ctypes.c_uint32 * 4)(OP["COL"], OP["CONST"], OP["COL"] | 1 << 8, OP["WHERE"])
+    consts = (ctypes.c_uint64 * 1)(int(value) & 0xFFFFFFFFFFFFFFFF)
+    ptrs = (ctypes.c_void_p * 2)(mask.ptr, column.ptr)
+    dts = (ctypes.c_int * 2)(_lib.dtype_code(mask.dtype)[0], _lib.dtype_code(column.dtype)[0])
+    _lib.call("vh_expr_eval", code, 4, consts, 1, ptrs, dts, 2, len(column), _lib.dtype_code(column.dtype)[0], out.ptr)
+    return out
 
 
 def _combine_columns(df, ranges):
@@ -611,7 +635,7 @@ class GroupByBase:
         # that order and read back once (instead of the whole grid plus a host gather)
         key_col = self.key_df.columns.get(str(self.by[0].expression)) if dense1 else None
         self.device_finish = self.first_order and dense1 and key_col is not None and \
-            not np.ma.isMaskedArray(key_col) and np.dtype(key_col.dtype).kind in "iu" and all(
+            not _masked(key_col) and np.dtype(key_col.dtype).kind in "iu" and all(
             type(a) is vagg.AggregatorDescriptorBasic and a.name in ("AggCount", "AggSum", "AggMin", "AggMax")
             and a.selection in (None, False) for _, a in parsed)
         self.descs = {}

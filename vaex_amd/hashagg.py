@@ -119,6 +119,9 @@ class HashAgg:
         return keys, counts, sums, nonnull
 
 
+from .device import is_masked_column as _masked  # noqa: E402  (the fused pass declines np.ma and DeviceMaskedArray)
+
+
 def eligible_key(df, by, allow_filtered=False):
     """The key column name when ``by`` is one plain, unmasked, native integer column on an
     unfiltered frame (the fused path's key), else None.  allow_filtered: filtered frames too
@@ -133,7 +136,7 @@ def eligible_key(df, by, allow_filtered=False):
     if (df.filtered and not allow_filtered) or by not in df.columns or df.is_category(by):
         return None
     key = df.columns[by]
-    if np.ma.isMaskedArray(key) or np.dtype(key.dtype).name not in KEY_DTYPES:
+    if _masked(key) or np.dtype(key.dtype).name not in KEY_DTYPES:
         return None
     if isinstance(key, np.ndarray) and (key.ndim != 1 or not key.dtype.isnative):
         return None
@@ -165,7 +168,7 @@ def _plan(df, by, actions, parse):
             return None
         c = df.columns[col]
         dt = np.dtype(c.dtype)
-        if np.ma.isMaskedArray(c) or dt.kind not in VALUE_KINDS or not dt.isnative:
+        if _masked(c) or dt.kind not in VALUE_KINDS or not dt.isnative:
             return None
         if isinstance(c, np.ndarray) and c.ndim != 1:
             return None

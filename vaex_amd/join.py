@@ -8,8 +8,8 @@ import re
 import numpy as np
 
 from . import _lib, hostops
-from .device import DeviceArray
-from .superutils import index_matched, index_type_from_dtype, take_device
+from .device import DeviceArray, DeviceMaskedArray
+from .superutils import index_matched, index_type_from_dtype, mask_combine, take_device
 
 
 def _ensure_string(e):
@@ -48,6 +48,8 @@ def index(df, expression, prime_growth=False, cardinality=None):
     ix = cls(initial_capacity=cap)
     for i1, i2 in _chunks(df):
         ar = df._eval_host(expression, i1, i2)
+        if isinstance(ar, DeviceMaskedArray):
+            raise NotImplementedError(f"an index over the masked HBM expression {expression!r} is not supported")
         select = None
         if df.filtered:
             select = df.device_keep_mask(i1, i2) if df.is_device_resident() else df.evaluate_filter_mask(i1, i2)
@@ -77,12 +79,24 @@ def gather(columns, lookup, length, masked=False):
     """{name: column[lookup]} for host and HBM columns of ``length`` rows; ``lookup`` (host or
     DeviceArray, int32 / int64) may hold -1 only with masked=True, and every column then comes
     back as a host ``np.ma`` array with those rows masked (an HBM column is read back together
-    with the mask the gather kernel wrote)."""
+    with the mask the gather kernel wrote).  A masked HBM column (DeviceMaskedArray) is gathered as
+    data plus mask, the mask one more uint8 column of ``vh_take``, and stays in HBM; a row whose
+    lookup is -1 is missing in it.  masked=True (the join's unmatched rows) does not take one."""
     out = {}
     from .strings import DeviceStringArray
     dev_names = [k for k, c in columns.items() if isinstance(c, DeviceArray)]
     str_names = [k for k, c in columns.items() if isinstance(c, DeviceStringArray)]
-    host_names = [k for k in columns if k not in dev_names and k not in str_names]
+    mdev_names = [k for k, c in columns.items() if isinstance(c, DeviceMaskedArray)]
+    host_names = [k for k in columns if k not in dev_names and k not in str_names and k not in mdev_names]
+    if mdev_names:
+        if masked:
+            raise NotImplementedError(f"masked HBM column {mdev_names[0]!r}: a gather that leaves rows unmatched (join) "
+                                      "is not supported")
+        dl = _device_indices(lookup, length)
+        cols = [columns[k].data for k in mdev_names] + [columns[k].mask for k in mdev_names]
+        res, miss = take_device(cols, dl, with_mask=True)
+        for j, k in enumerate(mdev_names):
+            out[k] = DeviceMaskedArray(res[j], mask_combine(res[len(mdev_names) + j], miss, "or"))
     if str_names:  # string columns: the byte-exact device gather (vh_str_take)
         if masked:
             raise NotImplementedError("string columns carry no nulls: a gather that leaves rows unmatched")
@@ -220,6 +234,10 @@ def join(df, other, on=None, left_on=None, right_on=None, lprefix="", rprefix=""
          allow_duplication=False, prime_growth=False, cardinality_other=None, inplace=False):
     left, right = df, other
     inner = False
+    for frame in (df, other):  # masked HBM columns do not join yet, as a key or as a payload
+        if frame._has_masked():
+            raise NotImplementedError(f"join of a frame with the masked HBM column {frame._masked_names()[0]!r} is "
+                                      "not supported")
     if how == "right":  # join.py:136-140
         left, right = right, left
         lprefix, rprefix = rprefix, lprefix

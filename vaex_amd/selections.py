@@ -119,7 +119,7 @@ class Selection(object):
         applied (``DataFrame.device_keep_mask`` ands it in)."""
         folded = self.fold(df)
         if folded is not None:
-            return df._eval_device(folded, i1, i2)
+            return df._eval_row_mask(folded, i1, i2)  # a missing value selects nothing
         return self._evaluate_device(df, i1, i2)
 
     def _own_expression(self, df):
@@ -130,7 +130,7 @@ class Selection(object):
         """A node with an expression of its own behind a chain that does not fold."""
         from .superutils import mask_combine
         previous_mask = self.previous_selection.evaluate_device(df, i1, i2)
-        current_mask = df._eval_device(self._own_expression(df), i1, i2)
+        current_mask = df._eval_row_mask(self._own_expression(df), i1, i2)
         return mask_combine(previous_mask, current_mask, self.mode)
 
     def __repr__(self):
@@ -250,11 +250,15 @@ class SelectionDropNa(Selection):
                     mode=self.mode, previous_selection=self._previous_dict())
 
     def _own_expression(self, df):
-        """On an HBM frame (its columns carry no masks) the node is the expression
-        ``~isnan(a) & ~isnan(b) ...``; on a host frame it has none (masked columns)."""
+        """On an HBM frame the node is the expression ``~isnan(a) & ~isnan(b) ...``, with a
+        ``notmissing(c)`` term for every masked HBM column among them; on a host frame it has
+        none (``np.ma`` columns are read node by node)."""
         if df is None or not df.is_device_resident():
             return None
         terms = ["~isnan(%s)" % name for name in self.column_names] if self.drop_nan else []
+        if self.drop_masked:  # the masked HBM columns among them (DeviceMaskedArray)
+            terms += ["notmissing(%s)" % name for name in self.column_names
+                      if not np.ma.isMaskedArray(df.columns.get(name)) and df.is_masked(name)]
         return " & ".join(terms) if terms else "True"
 
     def fold(self, df=None):

@@ -10,7 +10,7 @@ host columns of a mixed frame are gathered on the host threads).  A frame with n
 uses NumPy for the same order."""
 import numpy as np
 
-from .device import DeviceArray
+from .device import DeviceArray, DeviceMaskedArray
 from .join import _chunks, _host_indices, take_rows
 from .strings import DeviceStringArray, encode, rank_codes
 from .superutils import argsort_device, mask_rows, take_device
@@ -33,7 +33,10 @@ def kept_rows(df):
 
 
 def compact_device(column, mask):
-    """``column[mask != 0]`` for a DeviceArray column and a device byte mask, in HBM."""
+    """``column[mask != 0]`` for a DeviceArray (or DeviceMaskedArray: data and mask) column and a
+    device byte mask, in HBM."""
+    if isinstance(column, DeviceMaskedArray):
+        return DeviceMaskedArray(*take_device([column.data, column.mask], mask_rows(mask)))
     return take_device([column], mask_rows(mask))[0]
 
 
@@ -70,6 +73,9 @@ def argsort(df, by, ascending=True):
         raise ValueError("sort needs at least one key")
     n = _rows(df)
     keys = [df._eval_host(b, 0, n) for b in bys]
+    for b, k in zip(bys, keys):
+        if isinstance(k, DeviceMaskedArray):
+            raise NotImplementedError(f"sort by the masked HBM column / expression {b!r} is not supported")
     keys = [_string_ranks(k) if isinstance(k, DeviceStringArray) else k for k in keys]
     rows = kept_rows(df) if df.filtered else None
     if not df.is_device_resident() or any(np.ma.isMaskedArray(k) for k in keys):

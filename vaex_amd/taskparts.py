@@ -12,7 +12,7 @@ import re
 import numpy as np
 
 from . import superagg
-from .device import DeviceArray
+from .device import DeviceArray, DeviceMaskedArray
 from .utils import find_type_from_dtype
 
 _ORDINAL_VALUES = re.compile(r"^_ordinal_values\((.+),\s*([A-Za-z_][A-Za-z0-9_]*)\)$")
@@ -56,6 +56,8 @@ def create_binner(df, spec):
 
 
 def _split_masked(block):
+    if isinstance(block, DeviceMaskedArray):  # an HBM column with missing values: both parts in HBM
+        return block.data, block.mask
     if np.ma.isMaskedArray(block):
         return block.data, np.ma.getmaskarray(block)
     return block, None
@@ -161,9 +163,28 @@ class TaskPartAggregation:
                     # nunique tells rows outside the selection (or an HBM frame's filter)
                     # from missing values (cpu.py:551-554)
                     agg.set_selection_mask(selection_mask)
+                missing = [e for e in desc.expressions if isinstance(blocks[e], DeviceMaskedArray)]
+                if missing and desc.name == "AggFirst":
+                    # the AggFirst kernels take no masks (first.hip, as the reference's): the value
+                    # under a missing row would be taken as if it were there
+                    raise NotImplementedError(f"first over the masked expression {missing[0]!r} is not supported (the "
+                                              "first aggregator takes no masks): fillmissing / dropmissing + extract() first")
+                if missing and device_filter and hasattr(agg, "set_selection_mask") and selection in (None, False):
+                    # the engine's nunique does not see a row outside its selection mask at all, and
+                    # an HBM frame's filter goes in as that mask: a missing value the filter keeps
+                    # would not count as the null it is on a host frame (whose filter compacts the
+                    # chunk), so this is refused and not answered one short
+                    raise NotImplementedError(f"nunique of the masked expression {missing[0]!r} on a filtered HBM frame "
+                                              "without a selection is not supported: extract() the frame first")
+                if missing:
+                    # masked HBM values: keep = filter & selection & notmissing(e)..., one cached
+                    # device mask (a plain masked column costs one `mask == 0` pass per block)
+                    selection_mask = self._device_valid_mask(selection, missing, i1, i2)
                 for i, expression in enumerate(desc.expressions):
                     block, mask = _split_masked(blocks[expression])
                     block = _prepare(block)
+                    if isinstance(mask, DeviceArray):
+                        mask = None  # folded into selection_mask above
                     if mask is not None:
                         if isinstance(selection_mask, DeviceArray):
                             raise NotImplementedError("masked host columns in a filtered / selected HBM frame")
@@ -177,6 +198,20 @@ class TaskPartAggregation:
                     agg.clear_data_mask()
         self.grid.bin(all_aggregators, N)
         self.has_values = True
+
+    def _device_valid_mask(self, selection, expressions, i1, i2):
+        """HBM frame: the device mask of the rows an aggregator takes when its value expressions
+        can be missing: filter & selection & notmissing(e) for every e in ``expressions``."""
+        from . import selections as vsel
+        from .superutils import mask_combine
+        terms = " & ".join(f"notmissing({e})" for e in expressions)
+        if selection is None or selection is False:
+            return self.df.device_keep_mask(i1, i2, terms, cache=True)
+        resolved = self.df._resolve_selection(selection)
+        if isinstance(resolved, vsel.Selection):  # holds a lasso: its own mask, the rest and-ed in
+            return mask_combine(self.df.device_keep_mask(i1, i2, selection, cache=True),
+                                self.df.device_keep_mask(i1, i2, terms, cache=True), "and")
+        return self.df.device_keep_mask(i1, i2, f"({resolved}) & {terms}", cache=True)
 
     def reduce(self, others):
         for agg_index, (desc, selections, aggs, _) in enumerate(self.aggregations):
@@ -244,6 +279,15 @@ class TaskPartSetCreate:
                     self.set.update(ar)
             self._check_row_limit()
             return
+        if isinstance(ar, DeviceMaskedArray):
+            # a masked HBM column: its mask goes in as the set's mask (the null entry)
+            keep = None
+            if isinstance(filter_mask, DeviceArray) or self.selection:
+                keep = self.df.device_keep_mask(i1, i2, self.selection or None)
+            if len(ar):
+                self.set.update(ar.data, ar.mask, select=keep)
+            self._check_row_limit()
+            return
         if self.selection:
             sel = self.df.evaluate_selection_mask(self.selection, i1=i1, i2=i2, filter_mask=filter_mask)
             ar = ar[np.asarray(sel)]
@@ -282,13 +326,15 @@ class TaskPartValueCounts:
 
     def process(self, thread_index, i1, i2, filter_mask, blocks):
         ar = blocks[self.expression]
-        if isinstance(filter_mask, DeviceArray) or (isinstance(ar, DeviceArray) and self.selection):
+        if isinstance(filter_mask, DeviceArray) or (isinstance(ar, (DeviceArray, DeviceMaskedArray)) and self.selection):
             # HBM frame: filter & selection as one device mask, the counter skips the other rows
             keep = self.df.device_keep_mask(i1, i2, self.selection or None)
             if len(ar) == 0:
                 return
             if isinstance(ar, DeviceArray):
                 self.counter.update(ar, select=keep)
+            elif isinstance(ar, DeviceMaskedArray):
+                self.counter.update(ar.data, ar.mask, select=keep)
             else:  # a host (maybe masked) column of an HBM frame: counted where the mask is
                 data, mask = _split_masked(ar)
                 data = DeviceArray.from_numpy(_prepare(data))
@@ -302,6 +348,9 @@ class TaskPartValueCounts:
                 ar = ar.to_numpy()
             ar = ar[np.asarray(sel, dtype=bool)]
         if len(ar) == 0:
+            return
+        if isinstance(ar, DeviceMaskedArray):  # no filter, no selection: the mask alone
+            self.counter.update(ar.data, ar.mask)
             return
         if isinstance(ar, DeviceArray) or np.ma.isMaskedArray(ar):
             self.counter.update(ar)
@@ -338,7 +387,21 @@ class TaskPartMinMax:
         if isinstance(block, DeviceArray):
             # HBM frame: skip = ~(filter & selection), evaluated on the device
             skip = None
-            if isinstance(filter_mask, DeviceArray) or self.selection not in (None, False):
+            if isinstance(mask, DeviceArray):
+                # a masked HBM value: its missing rows are skipped with the unselected ones
+                from . import selections as vsel
+                from .superutils import mask_combine
+                selection = f"notmissing({self.expression})"
+                resolved = None if self.selection in (None, False) else self.df._resolve_selection(self.selection)
+                if isinstance(resolved, vsel.Selection):  # holds a lasso: its own mask, the rest and-ed in
+                    keep = mask_combine(self.df.device_keep_mask(i1, i2, self.selection),
+                                        self.df.device_keep_mask(i1, i2, selection), "and")
+                    skip = mask_combine(keep, None)
+                else:
+                    if resolved is not None:
+                        selection = f"({resolved}) & {selection}"
+                    skip = self.df.device_keep_mask(i1, i2, selection, invert=True)
+            elif isinstance(filter_mask, DeviceArray) or self.selection not in (None, False):
                 skip = self.df.device_keep_mask(i1, i2, self.selection if self.selection not in (None, False) else None,
                                                 invert=True)
             _lib.call("vh_minmax", block.ptr, len(block), code, flip, None if skip is None else skip.ptr,
